@@ -12,12 +12,14 @@ no data-path collective) and the final latents are all-gathered over RCCL once a
 `python -m torch.distributed.run --nproc-per-node N` (one rank per GPU, RCCL); under torchrun `--gpus` must equal
 WORLD_SIZE.  Clip ownership / seeds / the final gather are animate_anything_amd.distributed.
 
-`--workload svd` / `--workload rgba` print the same JSON schema (with `roofline` and `cpu_baseline`) for BASELINE.json
+`--workload svd` / `--workload rgba` print the same JSON schema (`--full`: with `roofline` and `cpu_baseline`) for BASELINE.json
 configs[3] (Stable-Video-Diffusion UNet, 14 frames x 576x1024) and configs[4] (the layerdiffuse RGBA path: the same UNet3D at
 16 frames x 384x384 plus its transparent-VAE add-ons, timed once per clip); the driver's default command stays configs[1].
 
-Prints ONE JSON line (rank 0).  `roofline` re-times the dominant kernel (the implicit-GEMM
-contraction: aa::conv_gemm_dma_kernel / conv3x3_slab_kernel / conv_gemm_x_kernel) in isolation with events on its own stream; `cpu_baseline` times the
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times `--steps` steps and prints `value` / `ms_per_step`;
+`--dump-outputs DIR` writes the latents the last timed step returned (DIR/latents.npy, float32).  The rest is measured with
+`--full` only: the other guidance form (`other_form`), `vae`, `rgba_addons`, `roofline` and `cpu_baseline`.  `roofline` re-times
+the dominant kernel (the implicit-GEMM contraction: aa::conv_gemm_dma_kernel / conv3x3_slab_kernel / conv_gemm_x_kernel) in isolation with events on its own stream; `cpu_baseline` times the
 CPU oracle (oracle/, a restatement of the reference: "port") on BASELINE.json configs[0] (8 frames x 256x256, the
 reference's own CPU-runnable case) - a full forward, median of 3 - and quotes the one full 16x512x512 forward measured
 offline on the same class of host (profiles/r02_cpu_baseline.json).
@@ -65,7 +67,17 @@ def parse():
                                                      "algorithmic bytes) as json: what scripts/pmc_traffic_report.py joins the per-dispatch PMC rows with")
     p.add_argument("--workload", default="unet3d", choices=["unet3d", "svd", "rgba"],
                    help="unet3d: BASELINE configs[1] (the metric of record); svd: configs[3]; rgba: configs[4]")
+    p.add_argument("--full", action="store_true",
+                   help="measure everything beside the headline too: the other guidance form and its 2-step cross-check, the contraction "
+                        "roofline (--gemm-breakdown), the VAE and RGBA add-on timings and the CPU baseline (each still off with its --no-* option). "
+                        "Without it a run sets up, warms up, times the steps and prints the result line")
+    p.add_argument("--dump-outputs", default="", metavar="DIR",
+                   help="after the timed steps write what the last timed step returned (the denoised latents) as DIR/<name>.npy, float32")
     a = p.parse_args()
+    if not a.full:
+        a.no_other_form = a.no_roofline = a.no_vae = a.no_cpu_baseline = True
+        if a.gemm_breakdown:
+            p.error("--gemm-breakdown is part of the roofline: add --full")
     if a.workload == "rgba" and a.size == 512:
         a.size = 384                                          # configs[4]: 16 frames x 384 x 384 (48 x 48 latents)
     return a
@@ -322,6 +334,17 @@ def vae_timing(dtype, device, ms_step):
                     "the 16 generated frames; = %.2f denoising steps of this run" % ((enc + dec) / ms_step)}
 
 
+def dump_outputs(out_dir, **arrays):
+    """`--dump-outputs DIR`: what the timed path returned in its last step, one float32 DIR/<name>.npy per array, so that two builds can
+    be compared output for output (same arguments = same seeded weights and inputs)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        arr = t.detach().float().cpu().numpy()
+        assert arr.nbytes <= 64 << 20, (name, arr.shape)
+        np.save(os.path.join(out_dir, f"{name}.npy"), arr)
+
+
 def respawn_under_torchrun(a, script):
     """`python bench.py --gpus N` (N > 1) outside torchrun: start N ranks on this node, one per GPU."""
     import socket
@@ -449,6 +472,8 @@ def run_svd(a, rank, world, device):
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
     assert torch.isfinite(x).all(), "non-finite latents"
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, latents=x)
     ms = dt / a.steps * 1e3
     # FLOP census of one step from the launches themselves: contractions from their descriptors, attention analytically
     unet.enable_graph(False)
@@ -600,6 +625,8 @@ def bench(a, selftest=False):
         dt = max(t.item() for t in tall)
     assert gathered.shape[0] == num_clips
     assert torch.isfinite(x).all() and torch.isfinite(gathered).all(), "non-finite latents"
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, latents=x, **({"latents_all_clips": gathered} if world > 1 else {}))
 
     # the other form of the step (shared prefix on <-> off), same number of steps, same protocol
     other = None
@@ -673,7 +700,7 @@ def bench(a, selftest=False):
         write_launch_list(a.launch_list, unet, lambda: run(ts[:1], inp["latents"]))
     if pinned:
         out["cpu_affinity"] = f"{len(pinned)} CPUs of the GPU's NUMA node"
-    if a.workload == "rgba" and rank == 0:
+    if a.workload == "rgba" and rank == 0 and a.full:
         out["rgba_addons"] = rgba_addons(dtype, device, a.frames, a.size)
     if a.workload == "unet3d" and rank == 0 and world == 1 and not selftest and not a.no_vae:
         out["vae"] = vae_timing(dtype, device, ms_step)

@@ -8,6 +8,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -25,7 +26,7 @@ def _run(args, env_extra, timeout=600, script="tests/bench_selftest.py"):
 
 
 def test_two_ranks_through_the_script_itself():
-    r = _run(["--gpus", "2", "--steps", "2", "--warmup", "1"], {})
+    r = _run(["--gpus", "2", "--steps", "2", "--warmup", "1", "--full"], {})
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout                     # rank 0 only, exactly one line
@@ -37,6 +38,23 @@ def test_two_ranks_through_the_script_itself():
     # whole-job value = clips of all ranks per second of the SLOWEST rank
     assert abs(out["value"] - 2 * 1e3 / max(out["per_rank_ms_per_step"])) / out["value"] < 0.02
     assert out["other_form"]["cfg_shared_prefix"] is True and out["other_form"]["value"] > 0
+
+
+def test_plain_run_dumps_the_last_step_and_repeats_it(tmp_path):
+    """Without --full the line holds the headline alone; --dump-outputs writes the latents of the last timed step, the same for the same
+    arguments from one process to the next."""
+    got = []
+    for i in range(2):
+        r = _run(["--gpus", "1", "--steps", "2", "--warmup", "1", "--dump-outputs", str(tmp_path / str(i))], {})
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, r.stdout
+        out = json.loads(lines[0])
+        assert out["steps"] == 2 and out["warmup"] == 1 and out["ms_per_step"] > 0 and out["other_form"] is None
+        assert not {"roofline", "cpu_baseline", "vae"} & set(out)
+        got.append(np.load(tmp_path / str(i) / "latents.npy"))
+    assert got[0].dtype == np.float32 and got[0].shape == (1, 4, 2, 5, 6) and np.isfinite(got[0]).all()
+    assert np.array_equal(got[0], got[1])
 
 
 def test_world_size_mismatch_is_refused():
