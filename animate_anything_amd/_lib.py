@@ -83,6 +83,21 @@ class AaLinearRows(C.Structure):
     ]
 
 
+class AaQuantRowsFp8(C.Structure):
+    _fields_ = [
+        ("x", C.c_void_p), ("gamma", C.c_void_p), ("beta", C.c_void_p), ("q", C.c_void_p), ("scale", C.c_void_p), ("rows", C.c_int64),
+        ("channels", C.c_int32), ("ldx", C.c_int32), ("ldq", C.c_int32), ("ln_eps", C.c_float), ("dtype", C.c_int32), ("_pad", C.c_int32),
+    ]
+
+
+class AaLinearFp8(C.Structure):
+    _fields_ = [
+        ("a", C.c_void_p), ("a_scale", C.c_void_p), ("w", C.c_void_p), ("w_scale", C.c_void_p), ("bias", C.c_void_p),
+        ("residual", C.c_void_p), ("out", C.c_void_p), ("rows", C.c_int64),
+        ("n", C.c_int32), ("k", C.c_int32), ("ld_res", C.c_int32), ("ldo", C.c_int32), ("geglu", C.c_int32), ("dtype", C.c_int32),
+    ]
+
+
 class AaDpmStep(C.Structure):
     _fields_ = [
         ("eps_uncond", C.c_void_p), ("eps_text", C.c_void_p), ("latents", C.c_void_p), ("x0_prev", C.c_void_p),
@@ -137,7 +152,7 @@ class AaEulerStepTok(C.Structure):
 
 
 SYMBOLS = ("aa_version", "aa_last_error", "aa_set_tile_override", "aa_conv_gemm_tile_info", "aa_conv_gemm_tile_ok", "aa_conv_gemm_workspace", "aa_conv_gemm", "aa_conv_gemm_launch_count", "aa_conv_gemm_row_stats_parts", "aa_conv_gemm_row_coef_ok", "aa_conv_gemm_tickets", "aa_conv_gemm_reduce_launches", "aa_conv_gemm_tile_flags", "aa_ln_finalize", "aa_groupnorm_workspace", "aa_groupnorm", "aa_groupnorm_coef", "aa_set_groupnorm_two_pass", "aa_groupnorm_plan",
-           "aa_layernorm", "aa_attention", "aa_seq_self_attention_ok", "aa_seq_self_attention", "aa_ff_fused_ok", "aa_ff_fused", "aa_linear_rows_ok", "aa_linear_rows", "aa_softmax_rows", "aa_cfg_dpm_step",
+           "aa_layernorm", "aa_attention", "aa_seq_self_attention_ok", "aa_seq_self_attention", "aa_ff_fused_ok", "aa_ff_fused", "aa_linear_rows_ok", "aa_linear_rows", "aa_quant_rows_fp8", "aa_linear_fp8", "aa_softmax_rows", "aa_cfg_dpm_step",
            "aa_timestep_embedding", "aa_pack_latents", "aa_cfg_dpm_step_tokens",
            "aa_blend", "aa_pack_frames", "aa_cfg_euler_step_tokens")
 
@@ -191,6 +206,8 @@ def bind(path: str) -> C.CDLL:
     lib.aa_groupnorm_coef.argtypes = [C.POINTER(AaGroupNorm), C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
     lib.aa_linear_rows_ok.argtypes = [C.POINTER(AaLinearRows)]
     lib.aa_linear_rows.argtypes = [C.POINTER(AaLinearRows), C.c_void_p]
+    lib.aa_quant_rows_fp8.argtypes = [C.POINTER(AaQuantRowsFp8), C.c_void_p]
+    lib.aa_linear_fp8.argtypes = [C.POINTER(AaLinearFp8), C.c_void_p]
     lib.aa_softmax_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]
     lib.aa_cfg_dpm_step.argtypes = [C.POINTER(AaDpmStep), C.c_void_p]
     lib.aa_timestep_embedding.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]

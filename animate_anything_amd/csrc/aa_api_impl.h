@@ -17,6 +17,7 @@
 #include "kernels/seq_attention.h"
 #include "kernels/ff_fused.h"
 #include "kernels/linear_rows.h"
+#include "kernels/linear_fp8.h"
 #include "kernels/glue.h"
 
 namespace aa {
@@ -899,6 +900,50 @@ int aa_linear_rows(const AaLinearRows* d, void* stream) {
     if (d->dtype == AA_F16) AA_LAUNCH((linear_rows_kernel<f16_t, 320>), grid, block, lr_lds_bytes(), stream, *d, n_full, n_split);
     else                    AA_LAUNCH((linear_rows_kernel<bf16_t, 320>), grid, block, lr_lds_bytes(), stream, *d, n_full, n_split);
     return finish("linear_rows");
+}
+
+int aa_quant_rows_fp8(const AaQuantRowsFp8* d, void* stream) {
+    using namespace aa;
+    if (!d) return fail(AA_E_SHAPE, "quant_rows_fp8: null descriptor");
+    if (d->rows <= 0 || d->channels <= 0 || d->channels % 16 || d->channels > 5120) return fail(AA_E_SHAPE, "quant_rows_fp8: rows=%lld channels=%d (a multiple of 16, at most 5120)", (long long)d->rows, d->channels);
+    if (d->ldx % 8 || d->ldq % 16 || d->ldx < d->channels || d->ldq < d->channels) return fail(AA_E_SHAPE, "quant_rows_fp8: row pitches ldx=%d ldq=%d", d->ldx, d->ldq);
+    if (!d->x || !d->q || !d->scale) return fail(AA_E_SHAPE, "quant_rows_fp8: x, q, scale are required");
+    if (!aligned16(d->x) || !aligned16(d->q) || !aligned16(d->gamma) || !aligned16(d->beta)) return fail(AA_E_ALIGN, "quant_rows_fp8: operands must be 16-byte aligned");
+    if (d->gamma && !(d->ln_eps > 0.0f)) return fail(AA_E_SHAPE, "quant_rows_fp8: LayerNorm needs ln_eps > 0");
+    if (d->dtype != AA_F16 && d->dtype != AA_BF16) return fail(AA_E_DTYPE, "quant_rows_fp8: unsupported dtype %d", d->dtype);
+    const dim3 grid((unsigned)((d->rows + 3) / 4)), block(256);
+    const int pieces = (d->channels + 1023) / 1024;         // 16-element pieces per lane
+#define AA_Q8(T, J) AA_LAUNCH((quant_rows_fp8_kernel<T, J>), grid, block, 0, stream, *d)
+    if (d->dtype == AA_F16) { if (pieces <= 1) AA_Q8(f16_t, 1); else if (pieces == 2) AA_Q8(f16_t, 2); else if (pieces == 3) AA_Q8(f16_t, 3); else AA_Q8(f16_t, 5); }
+    else                    { if (pieces <= 1) AA_Q8(bf16_t, 1); else if (pieces == 2) AA_Q8(bf16_t, 2); else if (pieces == 3) AA_Q8(bf16_t, 3); else AA_Q8(bf16_t, 5); }
+#undef AA_Q8
+    return finish("quant_rows_fp8");
+}
+
+int aa_linear_fp8(const AaLinearFp8* d, void* stream) {
+    using namespace aa;
+    if (!d) return fail(AA_E_SHAPE, "linear_fp8: null descriptor");
+    if (d->rows <= 0 || d->n <= 0 || d->k <= 0 || d->k % 128 || d->n % 64) return fail(AA_E_SHAPE, "linear_fp8: rows=%lld n=%d k=%d (k a multiple of 128, n of 64)", (long long)d->rows, d->n, d->k);
+    if (!d->a || !d->a_scale || !d->w || !d->w_scale || !d->out) return fail(AA_E_SHAPE, "linear_fp8: a, a_scale, w, w_scale, out are required");
+    if (d->geglu && d->residual) return fail(AA_E_SHAPE, "linear_fp8: the geglu epilogue takes no residual");
+    const int n_store = d->geglu ? d->n / 2 : d->n;
+    if (d->ldo % 8 || d->ldo < n_store || (d->residual && (d->ld_res % 8 || d->ld_res < n_store))) return fail(AA_E_SHAPE, "linear_fp8: row pitches ldo=%d ld_res=%d", d->ldo, d->ld_res);
+    const int64_t lim = (int64_t)1 << 31;
+    if (d->rows * d->k >= lim || (int64_t)d->n * d->k >= lim || d->rows * d->ldo * 2 >= lim || (d->residual && d->rows * d->ld_res * 2 >= lim))
+        return fail(AA_E_SHAPE, "linear_fp8: every operand must stay below 2 GiB");
+    if (!aligned16(d->a) || !aligned16(d->w) || !aligned16(d->w_scale) || !aligned16(d->bias) || !aligned16(d->residual) || !aligned16(d->out))
+        return fail(AA_E_ALIGN, "linear_fp8: operands must be 16-byte aligned");
+    if (d->dtype != AA_F16 && d->dtype != AA_BF16) return fail(AA_E_DTYPE, "linear_fp8: unsupported dtype %d", d->dtype);
+    const int tiles_m = (int)((d->rows + L8_BM - 1) / L8_BM), tiles_n = (d->n + L8_BN - 1) / L8_BN;
+    const dim3 grid((unsigned)(tiles_m * tiles_n)), block(256);
+    if (d->dtype == AA_F16) {
+        if (d->geglu) AA_LAUNCH((linear_fp8_kernel<f16_t, true>), grid, block, L8_LDS_BYTES, stream, *d, tiles_m, tiles_n);
+        else          AA_LAUNCH((linear_fp8_kernel<f16_t, false>), grid, block, L8_LDS_BYTES, stream, *d, tiles_m, tiles_n);
+    } else {
+        if (d->geglu) AA_LAUNCH((linear_fp8_kernel<bf16_t, true>), grid, block, L8_LDS_BYTES, stream, *d, tiles_m, tiles_n);
+        else          AA_LAUNCH((linear_fp8_kernel<bf16_t, false>), grid, block, L8_LDS_BYTES, stream, *d, tiles_m, tiles_n);
+    }
+    return finish("linear_fp8");
 }
 
 int aa_softmax_rows(const float* x, void* y, int64_t rows, int32_t cols, int32_t x_ld, int32_t y_ld, int32_t dtype, void* stream) {

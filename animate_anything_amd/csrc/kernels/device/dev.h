@@ -1,5 +1,5 @@
 // gfx950 device primitives used by every kernel: dynamic LDS base, 32x32x16 MFMA wrappers
-// (f16 / bf16 in, f32 accumulate), wave64 cross-lane exchange.  tests/emu/dev.h supplies
+// (f16 / bf16 in, f32 accumulate), the block-scaled 32x32x64 e4m3 form, wave64 cross-lane exchange.  tests/emu/dev.h supplies
 // host-side stand-ins with the same names so kernel bodies can be exercised on the CPU.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -18,6 +18,23 @@ __device__ __forceinline__ f32x16 mfma_32x32x16(f16_t, u32x4 a, u32x4 b, f32x16 
 }
 __device__ __forceinline__ f32x16 mfma_32x32x16(bf16_t, u32x4 a, u32x4 b, f32x16 c) {
     return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
+}
+
+// D = A(32x64) * B(64x32) + C with OCP e4m3 operands on the block-scaled form (v_mfma_scale_f32_32x32x64_f8f6f4, cbsz = blgp = 0: both
+// operands fp8 e4m3), both block scales E8M0 127 = 1.0: twice the rate of the 16-bit forms per clock.  Lane l supplies row (l&31) of A and
+// column (l&31) of B, 32 consecutive k bytes each (half-wave l>>5 picks which 32; lo = the first 16, hi = the second); D has the layout of every
+// 32x32 form (above).  The host stand-in lives in kernels/linear_fp8.h.
+__device__ __forceinline__ f32x16 mfma_scale_32x32x64_e4m3(u32x4 a_lo, u32x4 a_hi, u32x4 b_lo, u32x4 b_hi, f32x16 c) {
+    typedef int i32x8_ __attribute__((ext_vector_type(8)));
+    const i32x8_ a = {(int)a_lo[0], (int)a_lo[1], (int)a_lo[2], (int)a_lo[3], (int)a_hi[0], (int)a_hi[1], (int)a_hi[2], (int)a_hi[3]};
+    const i32x8_ b = {(int)b_lo[0], (int)b_lo[1], (int)b_lo[2], (int)b_lo[3], (int)b_hi[0], (int)b_hi[1], (int)b_hi[2], (int)b_hi[3]};
+    return __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a, b, c, 0, 0, 0, 0x7F7F7F7F, 0, 0x7F7F7F7F);
+}
+// four fp32 values (|v| <= 448) -> four OCP e4m3 bytes, round to nearest even (2 x v_cvt_pk_fp8_f32; byte 0 = a)
+__device__ __forceinline__ unsigned cvt4_e4m3(float a, float b, float c, float d) {
+    int r = __builtin_amdgcn_cvt_pk_fp8_f32(a, b, 0, false);
+    r = __builtin_amdgcn_cvt_pk_fp8_f32(c, d, r, true);
+    return (unsigned)r;
 }
 
 __device__ __forceinline__ float wave_shfl_xor(float v, int mask) { return __shfl_xor(v, mask, 64); }

@@ -230,7 +230,7 @@ def batch_eval(unet, text_encoder, vae, tokenizer, scheduler_config, validation_
 
 def main_eval(pretrained_model_path, validation_data, seed=None, motion_mask=None, motion_strength=None,
               output_dir="output/demo", iters=6, dtype="fp16", graph=True, lora_path=None, lora_rank=16,
-              unet_lora_modules=("UNet3DConditionModel",), guidance_parallel=False, **kwargs):
+              unet_lora_modules=("UNet3DConditionModel",), guidance_parallel=False, fp8_feedforward=False, **kwargs):
     """train.py:825-857.  Weights are cast to half precision on the GPU ("cuda" is the HIP device on ROCm).
     The reference accepts `motion_mask` / `motion_strength` here and never forwards them to the UNet constructor
     (train.py:838: the checkpoint's config.json governs); so do we - they are passed on only when the YAML sets them.
@@ -251,6 +251,8 @@ def main_eval(pretrained_model_path, validation_data, seed=None, motion_mask=Non
         if m is not None:
             m.requires_grad_(False)
             m.to(torch.device("cuda"), dtype=weight_dtype)
+    if fp8_feedforward:                                   # config key `fp8_feedforward: true`: the opt-in e4m3 FeedForward path
+        unet.enable_fp8_feedforward()
     if graph:
         unet.enable_graph()
     if world == 1:

@@ -109,6 +109,11 @@ LINEAR_ROWS = os.environ.get("AA_LINEAR_ROWS", "1") == "1"
 # ... and the GroupNorm in front of proj_in (affine-only: no SiLU behind it) applied to the rows in those registers: its statistics pass runs alone
 # (ops.groupnorm_coef), the normalised tensor is never written (AA_GN_FOLD=0: the statistics + normalise pair in front of proj_in).
 GN_FOLD = os.environ.get("AA_GN_FOLD", "1") == "1"
+# The FeedForward pair (GEGLU.proj, ff-out) of the wide transformers as W8A8 in OCP e4m3 (ops.quant_rows_fp8 / ops.linear_fp8, ABI 110): opt-in,
+# per model through UNet3DConditionModel.enable_fp8_feedforward(min_dim); AA_FP8_FF=1 switches it on in every UNet3DConditionModel at construction
+# (what lets an unchanged benchmark time it).  Off by default: the output differs from the 16-bit path by the quantisation error.
+AA_FP8_FF = os.environ.get("AA_FP8_FF", "0") == "1"
+FP8_FF_MIN_DIM = 640                 # 320 keeps its fused kernel (ops.ff_fused)
 LINEAR_ROWS_MIN = 16384              # below: a handful of 128-row workgroups that walk all output channels serially - the tile family is faster
 
 
@@ -511,6 +516,33 @@ class FeedForward(nn.Module):
     def __init__(self, dim, mult=4, dim_out=None):
         super().__init__()
         self.net = nn.ModuleList([GEGLU(dim, dim * mult), nn.Dropout(0.0), Linear(dim * mult, dim_out or dim)])
+        self.dim = dim
+        self.fp8 = False              # UNet3DConditionModel.enable_fp8_feedforward: `tokens_fp8` instead of the 16-bit contractions
+        self._pw8 = None
+        self._pw8_key = None
+
+    def _apply(self, fn, *a, **k):
+        self._pw8 = None
+        return super()._apply(fn, *a, **k)
+
+    def packed_fp8(self):
+        """(GEGLU.proj, ff-out) as e4m3 bytes + per-channel scales, built once from the weights as they are when first used (a LoRA is merged
+        into them before that: lora.merge edits the parameters in place, which this key notices)."""
+        w1, w2 = self.net[0].proj, self.net[2]
+        key = weights_key(w1.weight, w1.bias, w2.weight, w2.bias)
+        if self._pw8 is None or self._pw8_key != key:
+            self._pw8 = (ops.pack_weight_fp8(w1.weight, w1.bias, geglu=True), ops.pack_weight_fp8(w2.weight, w2.bias))
+            self._pw8_key = key
+        return self._pw8
+
+    def tokens_fp8(self, x, norm, residual):
+        """ff-out(GEGLU(norm(x))) + residual in e4m3: quantise (the LayerNorm inside) -> GEGLU contraction -> quantise -> ff-out contraction.
+        Four launches; the [tokens, 4 C] activation between the contractions is written and re-read in the storage type."""
+        p1, p2 = self.packed_fp8()
+        q, s = ops.quant_rows_fp8(x, ln=None if norm is None else (norm.weight, norm.bias, norm.eps))
+        h = ops.linear_fp8(q, s, p1, dtype=x.dtype)
+        q, s = ops.quant_rows_fp8(h)
+        return ops.linear_fp8(q, s, p2, residual=residual)
 
     def tokens(self, x, residual, ln=None, tail=None, out=None):
         """`tail` = (packed merged weights of _MergedTail, the transformer's outer residual[, ...]): ff-out, `+ residual` and the
@@ -566,7 +598,7 @@ class BasicTransformerBlock(nn.Module):
         `pre_in`: the transformer's proj_in (a Linear), NOT yet applied to x - it runs inside the first attention kernel (seq_pair_ok)."""
         fold = LN_FOLD
         ff_one = tail is not None and len(tail) > 2 and tail[2] is not None and ops.ff_fused_ok(x.shape[1], x.shape[0] * dup, x.dtype)
-        fold_ff = fold and LN_FOLD_FF and not ff_one          # (ops.ff_fused normalises its rows itself: no statistics from the producer)
+        fold_ff = fold and LN_FOLD_FF and not ff_one and not self.ff.fp8     # (ops.ff_fused / ops.quant_rows_fp8 normalise their rows themselves: no statistics from the producer)
         seq1 = self.attn1.seq_ok(x, g, temporal)
         seq2 = not self.attn2.is_cross and self.attn2.seq_ok(x, g, temporal)
         if seq1 and seq2 and SEQ_PRE and dup == 1:
@@ -579,6 +611,8 @@ class BasicTransformerBlock(nn.Module):
             a, x = self.attn2.seq_attention(a, self.norm2, g, pre=self.attn1.to_out[0], residual=x)
             r = self.attn2.to_out[0].tokens(a, residual=x, row_stats=fold_ff, coef_eps=self.norm3.eps)
             x, st = r if fold_ff else (r, None)
+            if self.ff.fp8:
+                return self.ff.tokens_fp8(x, self.norm3, residual=x)
             if ff_one:
                 return self.ff.fused_tokens(x, self.norm3, tail)
             if st is not None:
@@ -618,6 +652,8 @@ class BasicTransformerBlock(nn.Module):
             else:
                 r = self.attn2.self_tokens(xin, x, g, temporal, ln=ln2, rows_ln=self.norm2 if rows2 else None, row_stats=fold_ff, coef_eps=self.norm3.eps)
         x, st = r if fold_ff else (r, None)
+        if self.ff.fp8:
+            return self.ff.tokens_fp8(x, self.norm3, residual=x)
         if ff_one:
             return self.ff.fused_tokens(x, self.norm3, tail)
         if st is not None:
@@ -636,6 +672,8 @@ class _MergedTail:
         return super()._apply(fn, *a, **k)
 
     def merged_tail(self):
+        if self.transformer_blocks[-1].ff.fp8:             # an e4m3 FeedForward ends in its own contraction: proj_out runs as a 16-bit one behind it
+            return None
         ff_out = self.transformer_blocks[-1].ff.net[2]
         w2, b2, wp, bp = ff_out.weight, ff_out.bias, self.proj_out.weight, self.proj_out.bias
         hidden, dim = w2.shape[1], w2.shape[0]

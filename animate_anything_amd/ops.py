@@ -16,7 +16,7 @@ import torch
 
 from . import _lib
 from ._lib import (AA_ACT_GELU, AA_ACT_NONE, AA_ACT_QUICK_GELU, AA_ACT_SILU, AA_BF16, AA_F16, AA_F32, AaAttention, AaAttnOperand,
-                   AaBlend, AaConvGemm, AaFFFused, AaLinearRows, AaDpmStep, AaDpmStepTok, AaEulerStepTok, AaGroupNorm, AaPackFrames, AaPackLatents, AaSeqSelfAttn)
+                   AaBlend, AaConvGemm, AaFFFused, AaLinearRows, AaLinearFp8, AaQuantRowsFp8, AaDpmStep, AaDpmStepTok, AaEulerStepTok, AaGroupNorm, AaPackFrames, AaPackLatents, AaSeqSelfAttn)
 
 _DT = {torch.float16: AA_F16, torch.bfloat16: AA_BF16, torch.float32: AA_F32}
 
@@ -1048,6 +1048,96 @@ def linear_rows(x: torch.Tensor, pk: LinearRows, residual: Optional[torch.Tensor
             raise RuntimeError("linear_rows: `affine` must be groupnorm_coef's fp32 [groups, 2, channels] covering every row")
         d.row_affine, d.rows_per_group = _ptr(coef), per
     _run(lib.aa_linear_rows, C.byref(d), _stream(x))
+    return out
+
+
+# ------------------------------------------------------------------------------------- fp8 (e4m3) linear layers
+FP8_MAX = 448.0          # largest finite OCP e4m3 value
+FP8_TINY = 1e-12         # include/aa_mi355.h: AA_FP8_TINY
+
+
+def _fp8_row_perm(n: int, device) -> torch.Tensor:
+    """Row order of aa_linear_fp8's weight operand: inside every block of 32 rows, row i holds channel 16 * ((i >> 2) & 1) + 4 * (i >> 3) + (i & 3)."""
+    i = torch.arange(32, device=device)
+    perm = 16 * ((i >> 2) & 1) + 4 * (i >> 3) + (i & 3)
+    return (torch.arange(0, n, 32, device=device)[:, None] + perm[None, :]).reshape(-1)
+
+
+@dataclass
+class PackedWeightFp8:
+    """Operands of aa_linear_fp8: `w` uint8 [n, k] e4m3 bytes in the kernel's row order, `scale` / `bias` fp32 [n] in channel order
+    (geglu: value / gate blocks of 32 alternating, like pack_weight(geglu=True))."""
+    w: torch.Tensor
+    scale: torch.Tensor
+    bias: Optional[torch.Tensor]
+    n: int
+    k: int
+    geglu: bool
+
+    @property
+    def n_out(self):
+        return self.n // 2 if self.geglu else self.n
+
+
+def pack_weight_fp8(weight: torch.Tensor, bias: Optional[torch.Tensor] = None, geglu: bool = False) -> PackedWeightFp8:
+    """nn.Linear [n, k] -> e4m3 bytes with one fp32 scale per output channel: scale = max(absmax(row), FP8_TINY) / 448,
+    byte = float8_e4m3fn(weight / scale) (round to nearest even; |weight / scale| <= 448 by construction)."""
+    n, k = weight.shape
+    if k % 128 or n % 64 or (geglu and (n // 2) % 32):
+        raise RuntimeError(f"pack_weight_fp8: n={n} k={k} (k a multiple of 128, n of 64)")
+    dev = weight.device
+    wf = weight.detach().float()
+    b = None if bias is None else bias.detach().float()
+    if geglu:
+        d = n // 2
+        val = torch.arange(d, device=dev).reshape(d // 32, 1, 32)
+        src = torch.cat([val, val + d], dim=1).reshape(-1)
+        wf = wf[src]
+        b = None if b is None else b[src]
+    scale = wf.abs().amax(dim=1).clamp_min(FP8_TINY) / FP8_MAX
+    q = (wf / scale[:, None]).clamp(-FP8_MAX, FP8_MAX).cpu().to(torch.float8_e4m3fn).view(torch.uint8).to(dev)
+    return PackedWeightFp8(q[_fp8_row_perm(n, dev)].contiguous(), scale.contiguous(), None if b is None else b.contiguous(), n, k, bool(geglu))
+
+
+def quant_rows_fp8(x: torch.Tensor, ln=None, out=None):
+    """Per-row dynamic quantisation of a token matrix [M, K] to e4m3: (q uint8 [M, K], scale fp32 [M]) with scale = max(absmax(row), FP8_TINY) / 448.
+    `ln` = (gamma, beta, eps): the rows of LayerNorm(x) are quantised instead (one pass, statistics in fp32).  `out` = (q, scale) buffers to fill."""
+    lib = _lib.get()
+    gamma, beta, eps = ln if ln is not None else (None, None, 0.0)
+    q, scale = out if out is not None else (torch.empty(x.shape, dtype=torch.uint8, device=x.device),
+                                            torch.empty(x.shape[0], dtype=torch.float32, device=x.device))
+    _check(x, gamma, beta, q, scale)
+    if q.dtype != torch.uint8 or scale.dtype != torch.float32 or tuple(q.shape) != tuple(x.shape) or scale.numel() != x.shape[0]:
+        raise RuntimeError("quant_rows_fp8: `out` must be (uint8 [M, K], fp32 [M])")
+    if ln is not None and (gamma.dtype != x.dtype or (beta is not None and beta.dtype != x.dtype) or gamma.numel() != x.shape[1]):
+        raise RuntimeError("quant_rows_fp8: LayerNorm parameters must match x")
+    d = AaQuantRowsFp8()
+    d.x, d.gamma, d.beta, d.q, d.scale = _ptr(x), _ptr(gamma), _ptr(beta), _ptr(q), _ptr(scale)
+    d.rows, d.channels, d.ldx, d.ldq, d.ln_eps, d.dtype = x.shape[0], x.shape[1], x.stride(0), q.stride(0), float(eps), _DT[x.dtype]
+    _run(lib.aa_quant_rows_fp8, C.byref(d), _stream(x))
+    return q, scale
+
+
+def linear_fp8(q: torch.Tensor, scale: torch.Tensor, packed: PackedWeightFp8, residual: Optional[torch.Tensor] = None,
+               out: Optional[torch.Tensor] = None, dtype=None) -> torch.Tensor:
+    """(q scale) W^T + b (+ residual) on the block-scaled e4m3 matrix form (q, scale from quant_rows_fp8, `packed` from pack_weight_fp8);
+    a geglu pack gives value * gelu(gate), [M, n / 2].  The output type is the residual's / `out`'s, or `dtype`."""
+    lib = _lib.get()
+    _check(q, scale, packed.w, packed.scale, packed.bias, residual, out)
+    if q.dtype != torch.uint8 or q.dim() != 2 or q.shape[1] != packed.k or scale.dtype != torch.float32 or scale.numel() != q.shape[0]:
+        raise RuntimeError("linear_fp8: (q, scale) must be quant_rows_fp8's uint8 [M, K] / fp32 [M] with the K of the packed weights")
+    if out is None:
+        dt = residual.dtype if residual is not None else dtype
+        if dt is None:
+            raise RuntimeError("linear_fp8: give `out`, `residual` or `dtype`")
+        out = torch.empty(q.shape[0], packed.n_out, dtype=dt, device=q.device)
+    if residual is not None and (residual.dtype != out.dtype or residual.shape != out.shape):
+        raise RuntimeError("linear_fp8: the residual must have the output's type and shape")
+    d = AaLinearFp8()
+    d.a, d.a_scale, d.w, d.w_scale, d.bias = _ptr(q), _ptr(scale), _ptr(packed.w), _ptr(packed.scale), _ptr(packed.bias)
+    d.residual, d.out, d.rows, d.n, d.k = _ptr(residual), _ptr(out), q.shape[0], packed.n, packed.k
+    d.ld_res, d.ldo, d.geglu, d.dtype = 0 if residual is None else residual.stride(0), out.stride(0), int(packed.geglu), _DT[out.dtype]
+    _run(lib.aa_linear_fp8, C.byref(d), _stream(q))
     return out
 
 

@@ -222,6 +222,9 @@ class UNet3DConditionModel(nn.Module):
         self.conv_act = nn.SiLU()
         self.conv_out = Conv2d(ch0, out_channels, 3, padding=1)
         self._graph = None
+        from . import layers as _layers
+        if _layers.AA_FP8_FF:                                  # (the module-level knob: see enable_fp8_feedforward)
+            self.enable_fp8_feedforward()
 
     # ------------------------------------------------------------------ nn.Module / diffusers protocol
     @property
@@ -431,6 +434,30 @@ class UNet3DConditionModel(nn.Module):
         """Capture the forward (timestep embedding + input packing + `_core`) in a hipGraph on first use per input
         signature and replay it afterwards (removes ~1k host launches per denoising step)."""
         self._graph = {} if enabled else None
+
+    def enable_fp8_feedforward(self, min_dim=None):
+        """Opt in to the W8A8 (OCP e4m3) FeedForward path: every spatial and temporal transformer FeedForward with `dim >= min_dim` (default
+        layers.FP8_FF_MIN_DIM = 640; the 320-channel ones keep their fused kernel) runs quantise -> GEGLU contraction -> quantise -> ff-out
+        contraction on the block-scaled fp8 matrix form.  The e4m3 weights are derived from the parameters on first use (after a LoRA merge
+        they are derived again).  The output differs from the 16-bit path by the quantisation error: off by default.  Returns the number of
+        FeedForwards flagged."""
+        from .layers import FP8_FF_MIN_DIM, FeedForward
+        min_dim = FP8_FF_MIN_DIM if min_dim is None else min_dim
+        n = 0
+        for m in self.modules():
+            if isinstance(m, FeedForward):
+                m.fp8 = m.dim >= min_dim
+                n += int(m.fp8)
+        self.invalidate_caches()                               # (captured graphs replay the other path's launches)
+        return n
+
+    def disable_fp8_feedforward(self):
+        from .layers import FeedForward
+        for m in self.modules():
+            if isinstance(m, FeedForward):
+                m.fp8 = False
+                m._pw8 = None
+        self.invalidate_caches()
 
     def session(self, batch, frames, h, w, text_shape, use_mask, has_motion, has_cond_emb, sample_dtype, sample_batch,
                 cond_batch, mask_batch, device, cfg_dup=False):

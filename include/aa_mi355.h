@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define AA_VERSION 109
+#define AA_VERSION 110
 
 enum { AA_F16 = 0, AA_BF16 = 1, AA_F32 = 2 };
 enum { AA_OK = 0, AA_E_SHAPE = -1, AA_E_DTYPE = -2, AA_E_ALIGN = -3, AA_E_WORKSPACE = -4, AA_E_HIP = -5 };
@@ -376,6 +376,59 @@ typedef struct AaLinearRows {
 
 int aa_linear_rows_ok(const AaLinearRows* d);
 int aa_linear_rows(const AaLinearRows* d, void* stream);
+
+/* ----------------------------------------------------------------------------------------------
+ * aa_quant_rows_fp8 / aa_linear_fp8 (version 110): an opt-in W8A8 path in OCP e4m3 (`e4m3fn`: bias 7, no infinities, 0x7F / 0xFF = NaN, largest
+ * finite value 448) for plain linear layers on token rows - the FeedForward pair of the 640- / 1280-channel transformers (diffusers GEGLU.proj and
+ * FeedForward.net[2] behind BasicTransformerBlock.norm3; reference models/unet_3d_blocks.py:287,446,681 / :379,526,759 via diffusers).
+ *
+ * aa_quant_rows_fp8: per-row dynamic quantisation, optionally of LayerNorm(x) (gamma != NULL; statistics and the normalised row in fp32, nothing
+ * is rounded to the storage type in between):
+ *     scale[r] = max(absmax(row r), AA_FP8_TINY) / 448        q[r][k] = e4m3(clamp(row[k] / scale[r], -448, 448)), round to nearest even
+ * Finite input never produces a NaN byte; an all-zero row gives zero bytes and the finite scale AA_FP8_TINY / 448.
+ * channels: a multiple of 16, at most 5120.
+ *
+ * aa_linear_fp8: out[m][n] = (sum_k a[m][k] w[n][k]) a_scale[m] w_scale[n] + bias[n] (+ residual[m][n]), products on the block-scaled matrix
+ * form with both block scales 1, fp32 accumulation, the scales and the bias applied in fp32, one rounding to the storage type.
+ * k a multiple of 128, n a multiple of 64, any rows >= 1.  `w` is [n][k] bytes with the ROWS of every block of 32 in the order
+ * 16 * ((i >> 2) & 1) + 4 * (i >> 3) + (i & 3) (i = 0..31: a lane's accumulator registers are then 16 consecutive channels); w_scale / bias are
+ * fp32 [n] in channel order.  geglu = 1: the blocks of 32 alternate value / gate channels of a GEGLU projection (block 2 j = value channels
+ * 32 j .., block 2 j + 1 = their gates; w_scale / bias in that block order) and out is [rows][n / 2] = value * gelu_erf(gate); no residual.
+ * ops.pack_weight_fp8 builds `w`, `w_scale` and `bias` (per-output-channel absmax / 448).
+ * ---------------------------------------------------------------------------------------------- */
+#define AA_FP8_TINY 1e-12f
+typedef struct AaQuantRowsFp8 {
+    const void* x;          /* [rows][ldx] storage dtype */
+    const void* gamma;      /* [channels] storage dtype: LayerNorm in front of the quantisation; NULL = x as it is */
+    const void* beta;       /* [channels] storage dtype; may be NULL */
+    void* q;                /* [rows][ldq] e4m3 bytes */
+    float* scale;           /* [rows] */
+    int64_t rows;
+    int32_t channels;
+    int32_t ldx;            /* elements, a multiple of 8 */
+    int32_t ldq;            /* bytes, a multiple of 16 */
+    float ln_eps;
+    int32_t dtype;          /* AA_F16 | AA_BF16 */
+    int32_t _pad;
+} AaQuantRowsFp8;
+
+typedef struct AaLinearFp8 {
+    const void* a;          /* [rows][k] e4m3 bytes (dense: row pitch k) */
+    const float* a_scale;   /* [rows] */
+    const void* w;          /* [n][k] e4m3 bytes, packed row order (above) */
+    const float* w_scale;   /* [n] */
+    const float* bias;      /* [n]; may be NULL */
+    const void* residual;   /* [rows][ld_res] storage dtype; may be NULL (must be NULL with geglu) */
+    void* out;              /* [rows][ldo] storage dtype; n columns (geglu: n / 2) */
+    int64_t rows;
+    int32_t n, k;
+    int32_t ld_res, ldo;    /* elements, multiples of 8; a, w, out, residual < 2 GiB each */
+    int32_t geglu;
+    int32_t dtype;          /* AA_F16 | AA_BF16: out / residual */
+} AaLinearFp8;
+
+int aa_quant_rows_fp8(const AaQuantRowsFp8* d, void* stream);
+int aa_linear_fp8(const AaLinearFp8* d, void* stream);
 
 /* aa_softmax_rows: y[r, :] = softmax(x[r, :]) for fp32 scores (VAE mid-block single-head
  * attention, head_dim 512, where scores are materialised: diffusers Attention with
