@@ -1063,5 +1063,20 @@ int aa_cfg_euler_step_tokens(const AaEulerStepTok* d, void* stream) {
     return finish("cfg_euler_step_tokens");
 }
 
+int aa_cfg_ddim_step_tokens(const AaDdimStepTok* d, void* stream) {
+    using namespace aa;
+    if (!d || !d->tokens || !d->latents) return fail(AA_E_SHAPE, "cfg_ddim_step_tokens: null operand");
+    if (d->clips <= 0 || d->channels <= 0 || d->frames <= 0 || d->hw <= 0 || d->ld < d->channels || d->next_t_count < 0 || d->next_t_count > 256)
+        return fail(AA_E_SHAPE, "cfg_ddim_step_tokens: bad geometry");
+    if (d->c_n != 0.0f && !d->noise) return fail(AA_E_SHAPE, "cfg_ddim_step_tokens: c_n != 0 needs the noise operand");
+    int64_t blocks = ((int64_t)d->clips * d->channels * d->frames * d->hw + 255) / 256;
+    if (blocks > 2048) blocks = 2048;
+    const dim3 grid((unsigned)blocks), block(256);
+    if (d->dtype == AA_F16) AA_LAUNCH((cfg_ddim_step_tok_kernel<f16_t>), grid, block, 0, stream, *d);
+    else if (d->dtype == AA_BF16) AA_LAUNCH((cfg_ddim_step_tok_kernel<bf16_t>), grid, block, 0, stream, *d);
+    else return fail(AA_E_DTYPE, "cfg_ddim_step_tokens: unsupported dtype %d", d->dtype);
+    return finish("cfg_ddim_step_tokens");
+}
+
 }  // extern "C"
 #endif  // AA_TU_TILES_ONLY

@@ -5,6 +5,7 @@
 //                            zero-padded to 8 channels, classifier-free-guidance duplication of the batch
 //  * cfg_dpm_step_tok_kernel aa_cfg_dpm_step reading the UNet's token-layout output (frame 0 dropped, :522) and writing
 //                            the next UNet input
+//  * cfg_ddim_step_tok_kernel the same for DDIMScheduler.step (the scheduler the checkpoints ship; reference app.py:64-113)
 #pragma once
 #include "dev.h"
 #include "aa_mi355.h"
@@ -78,6 +79,39 @@ __global__ void __launch_bounds__(256) cfg_dpm_step_tok_kernel(const AaDpmStepTo
         const float nx = p.c_x * xi - p.c_d0 * x0 - p.c_d1 * (x0 - x0p[i]);
         x[i] = nx;
         x0p[i] = x0;
+        if (p.latents_lp) reinterpret_cast<T*>(p.latents_lp)[i] = (T)nx;
+    }
+}
+
+// guidance + DDIMScheduler.step with the scalars folded by the caller (aa_mi355.h AaDdimStepTok); token addressing of
+// cfg_dpm_step_tok_kernel.  fp32 throughout; `noise` is read only when c_n != 0 (the entry point refuses a null one then).
+template <typename T>
+__global__ void __launch_bounds__(256) cfg_ddim_step_tok_kernel(const AaDdimStepTok p) {
+    const T* tok = reinterpret_cast<const T*>(p.tokens);
+    float* x = reinterpret_cast<float*>(p.latents);
+    const int T1 = p.frames + 1;
+    const int64_t n = (int64_t)p.clips * p.channels * p.frames * p.hw;
+    if (p.next_t && blockIdx.x == 0 && threadIdx.x < p.next_t_count) p.next_t[threadIdx.x] = p.next_t_value;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+        const int pix = (int)(i % p.hw);
+        int64_t r = i / p.hw;
+        const int f = (int)(r % p.frames); r /= p.frames;
+        const int c = (int)(r % p.channels);
+        const int b = (int)(r / p.channels);
+        const int64_t tok_u = ((int64_t)b * T1 + f + 1) * p.hw + pix;                   // frame 0 of the UNet output is dropped (:522)
+        const float u = (float)tok[tok_u * p.ld + c];
+        float m = u;
+        if (p.guidance_on) {
+            const int64_t tok_t = ((int64_t)(p.clips + b) * T1 + f + 1) * p.hw + pix;   // [uncond clips | text clips] (pipeline.py:165)
+            m = u + p.guidance * ((float)tok[tok_t * p.ld + c] - u);
+        }
+        const float xi = x[i];
+        float x0 = p.a_x * xi + p.a_m * m;
+        if (p.clip_on) x0 = fminf(fmaxf(x0, -p.clip), p.clip);
+        const float e = p.eps_from_x0 ? p.q_x * xi + p.q_0 * x0 : p.e_x * xi + p.e_m * m;
+        float nx = p.c_0 * x0 + p.c_e * e;
+        if (p.c_n != 0.0f) nx += p.c_n * p.noise[i];
+        x[i] = nx;
         if (p.latents_lp) reinterpret_cast<T*>(p.latents_lp)[i] = (T)nx;
     }
 }

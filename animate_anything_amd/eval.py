@@ -4,7 +4,8 @@
     python -m animate_anything_amd.eval --config <ckpt>/config.yaml --eval validation_data.prompt_image=img.jpg ...
 
 Same YAML keys and dot-list overrides (`pretrained_model_path`, `validation_data.{prompt,prompt_image,mask,strength,
-num_frames,width,height,num_inference_steps,guidance_scale,fps}`, `seed`, `motion_mask`, `motion_strength`).
+num_frames,width,height,num_inference_steps,guidance_scale,fps}`, `seed`, `motion_mask`, `motion_strength`), plus
+`sampler: ddim` for the checkpoint's own DDIM scheduler in place of DPM-Solver++.
 The third-party pieces the reference pulls in and that do not exist in this image are replaced by small
 equivalents: OmegaConf -> PyYAML + dot-list merge, `VaeImageProcessor.preprocess` -> PIL lanczos resize + [-1,1]
 scaling, torchvision `ToTensor`/`Resize(antialias=False)` -> torch bilinear interpolate, imageio -> PIL GIF writer.
@@ -28,7 +29,7 @@ from PIL import Image
 
 from .pipeline import (DDPM_forward_timesteps, LatentToVideoPipeline, calculate_latent_motion_score,
                        tensor_to_vae_latent)
-from .schedulers import DDPMScheduler, DPMSolverMultistepScheduler
+from .schedulers import DDIMScheduler, DDPMScheduler, DPMSolverMultistepScheduler
 from .unet3d import UNet3DConditionModel
 from .vae import AutoencoderKL
 
@@ -200,12 +201,15 @@ def eval(pipeline, validation_data, out_file, index, forward_t=25, preview=True,
 
 def batch_eval(unet, text_encoder, vae, tokenizer, scheduler_config, validation_data, output_dir, preview,
                global_step=0, iters=6, generator=None, indices=None, seed=None, lora_path=None, lora_rank=16,
-               unet_lora_modules=("UNet3DConditionModel",), guidance_group=None):
-    """train.py:793-823: pipeline with DPM-Solver++ built from the checkpoint's scheduler config, `iters` samples.
+               unet_lora_modules=("UNet3DConditionModel",), guidance_group=None, sampler="dpm"):
+    """train.py:793-823: pipeline with DPM-Solver++ built from the checkpoint's scheduler config, `iters` samples
+    (`sampler="ddim"`: DDIM from the same config, the scheduler the reference's app keeps, app.py:65).
     `indices` (clip sharding, main_eval): render only these sample indices, each with its own generator seeded
     `seed + index` (distributed.clip_seed) so that a sample does not depend on which rank renders it."""
     unet.eval()
-    scheduler = DPMSolverMultistepScheduler.from_config(scheduler_config)
+    if sampler not in ("dpm", "ddim"):
+        raise ValueError(f"sampler {sampler!r}: dpm (DPM-Solver++, the default) or ddim")
+    scheduler = (DDIMScheduler if sampler == "ddim" else DPMSolverMultistepScheduler).from_config(scheduler_config)
     pipeline = LatentToVideoPipeline(vae=vae, text_encoder=text_encoder, tokenizer=tokenizer, unet=unet,
                                      scheduler=scheduler)
     pipeline.guidance_group = guidance_group              # latency mode: the guidance halves of a clip on the two GPUs of a pair
@@ -230,7 +234,7 @@ def batch_eval(unet, text_encoder, vae, tokenizer, scheduler_config, validation_
 
 def main_eval(pretrained_model_path, validation_data, seed=None, motion_mask=None, motion_strength=None,
               output_dir="output/demo", iters=6, dtype="fp16", graph=True, lora_path=None, lora_rank=16,
-              unet_lora_modules=("UNet3DConditionModel",), guidance_parallel=False, fp8_feedforward=False, **kwargs):
+              unet_lora_modules=("UNet3DConditionModel",), guidance_parallel=False, fp8_feedforward=False, sampler="dpm", **kwargs):
     """train.py:825-857.  Weights are cast to half precision on the GPU ("cuda" is the HIP device on ROCm).
     The reference accepts `motion_mask` / `motion_strength` here and never forwards them to the UNet constructor
     (train.py:838: the checkpoint's config.json governs); so do we - they are passed on only when the YAML sets them.
@@ -238,6 +242,8 @@ def main_eval(pretrained_model_path, validation_data, seed=None, motion_mask=Non
     Under `torchrun` (WORLD_SIZE > 1: BASELINE.json configs[2], "bs=8, 1 clip/GPU") the `iters` samples of the clip batch
     are sharded round-robin over the ranks (rank r renders samples r, r+W, ...; per-sample seed = seed + index so the
     outputs do not depend on W) and the final latents are all-gathered over RCCL (distributed.gather_clips)."""
+    if sampler not in ("dpm", "ddim"):                    # (before any model is loaded)
+        raise ValueError(f"sampler {sampler!r}: dpm (DPM-Solver++, the default) or ddim")
     from . import distributed as D
     rank, world, _dev = D.init()
     generator = None
@@ -257,7 +263,7 @@ def main_eval(pretrained_model_path, validation_data, seed=None, motion_mask=Non
         unet.enable_graph()
     if world == 1:
         return batch_eval(unet, text_encoder, vae, tokenizer, scfg, validation_data, output_dir, True, iters=iters,
-                          generator=generator, lora_path=lora_path, lora_rank=lora_rank, unet_lora_modules=unet_lora_modules)
+                          generator=generator, lora_path=lora_path, lora_rank=lora_rank, unet_lora_modules=unet_lora_modules, sampler=sampler)
     if guidance_parallel:
         # latency mode (`guidance_parallel=true`): ranks (2p, 2p+1) share one clip - unconditional / text half of its guidance
         # batch - and exchange the UNet outputs every step; the clips are sharded over the pairs; rank 2p writes the files
@@ -265,11 +271,11 @@ def main_eval(pretrained_model_path, validation_data, seed=None, motion_mask=Non
         return batch_eval(unet, text_encoder, vae, tokenizer, scfg, validation_data, output_dir, role == 0, iters=iters,
                           indices=D.clip_indices(iters, pair, world // 2), seed=seed if seed is not None else 0,
                           lora_path=lora_path, lora_rank=lora_rank, unet_lora_modules=unet_lora_modules,
-                          guidance_group=(role, group))
+                          guidance_group=(role, group), sampler=sampler)
     mine = D.clip_indices(iters, rank, world)
     results = batch_eval(unet, text_encoder, vae, tokenizer, scfg, validation_data, output_dir, True, iters=iters,
                          generator=generator, indices=mine, seed=seed, lora_path=lora_path, lora_rank=lora_rank,
-                         unet_lora_modules=unet_lora_modules)
+                         unet_lora_modules=unet_lora_modules, sampler=sampler)
     local = torch.stack([r[2][0] for r in results]) if results else None
     shape = [0] * 5
     if local is not None:

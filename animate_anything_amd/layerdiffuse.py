@@ -235,7 +235,7 @@ class MaskedLatentToVideoPipeline(LatentToVideoPipeline):
         if timesteps is None:
             timesteps = self.scheduler.timesteps
         x = self.denoise(latents, prompt_embeds, condition_latent, mask, motion, [int(t) for t in timesteps], guidance_scale,
-                         callback, callback_steps)
+                         callback, callback_steps, eta=eta, generator=generator)
         latents = x.to(self.unet.dtype)
         video_tensor = self.decode_latents(latents)
         pngs, alpha_jpg, pngs_rgb = decode_rgba(video_tensor, latents, vae_alpha_decoder)

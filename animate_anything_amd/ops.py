@@ -16,7 +16,7 @@ import torch
 
 from . import _lib
 from ._lib import (AA_ACT_GELU, AA_ACT_NONE, AA_ACT_QUICK_GELU, AA_ACT_SILU, AA_BF16, AA_F16, AA_F32, AaAttention, AaAttnOperand,
-                   AaBlend, AaConvGemm, AaFFFused, AaLinearRows, AaLinearFp8, AaQuantRowsFp8, AaDpmStep, AaDpmStepTok, AaEulerStepTok, AaGroupNorm, AaPackFrames, AaPackLatents, AaSeqSelfAttn)
+                   AaBlend, AaConvGemm, AaFFFused, AaLinearRows, AaLinearFp8, AaQuantRowsFp8, AaDdimStepTok, AaDpmStep, AaDpmStepTok, AaEulerStepTok, AaGroupNorm, AaPackFrames, AaPackLatents, AaSeqSelfAttn)
 
 _DT = {torch.float16: AA_F16, torch.bfloat16: AA_BF16, torch.float32: AA_F32}
 
@@ -1274,3 +1274,33 @@ def cfg_euler_step_tokens(v_tokens, latents, guidance, c_x, c_v, next_t=None, ne
     d.clips, d.channels, d.frames, d.hw, d.ld = clips, c, frames, h * w, v_tokens.stride(0)
     d.c_x, d.c_v, d.dtype = float(c_x), float(c_v), _DT[v_tokens.dtype]
     _run(lib.aa_cfg_euler_step_tokens, C.byref(d), _stream(latents))
+
+
+def cfg_ddim_step_tokens(tokens, latents, latents_lp, guidance, coeffs, noise=None, next_t=None, next_t_value=0.0):
+    """Fused CFG + DDIM update reading the UNet's token-layout output [(2*)clips*(T+1)*hw, ld]; latents fp32 [clips, C, T, h, w]
+    updated in place.  `coeffs` is schedulers.DDIMScheduler.coefficients(); `noise` (fp32, the latents' shape) is needed when
+    coeffs["c_n"] != 0 (eta > 0)."""
+    lib = _lib.get()
+    _check(tokens, latents, latents_lp, noise, next_t)
+    if latents.dtype != torch.float32 or latents.dim() != 5:
+        raise RuntimeError("cfg_ddim_step_tokens: latents must be fp32 [clips, C, T, h, w]")
+    if noise is not None and (noise.shape != latents.shape or noise.dtype != torch.float32):
+        raise RuntimeError("cfg_ddim_step_tokens: noise must be fp32 in the latents' shape")
+    if latents_lp is not None and (latents_lp.shape != latents.shape or latents_lp.dtype != tokens.dtype):
+        raise RuntimeError("cfg_ddim_step_tokens: latents_lp must have the latents' shape and the tokens' dtype")
+    if next_t is not None and next_t.dtype != torch.float32:
+        raise RuntimeError("cfg_ddim_step_tokens: next_t must be fp32")
+    clips, c, frames, h, w = latents.shape
+    rows = (2 if guidance is not None else 1) * clips * (frames + 1) * h * w
+    if tokens.dim() != 2 or tokens.shape[0] < rows or tokens.shape[1] < c:
+        raise RuntimeError(f"cfg_ddim_step_tokens: tokens {tuple(tokens.shape)} do not hold {rows} rows of {c} channels")
+    d = AaDdimStepTok()
+    d.tokens, d.latents, d.latents_lp, d.noise = _ptr(tokens), _ptr(latents), _ptr(latents_lp), _ptr(noise)
+    d.next_t, d.next_t_count, d.next_t_value = _ptr(next_t), 0 if next_t is None else next_t.numel(), float(next_t_value)
+    d.clips, d.channels, d.frames, d.hw, d.ld = clips, c, frames, h * w, tokens.stride(0)
+    d.guidance_on, d.guidance = int(guidance is not None), float(guidance or 0.0)
+    d.a_x, d.a_m, d.e_x, d.e_m, d.q_x, d.q_0 = (coeffs[k] for k in ("a_x", "a_m", "e_x", "e_m", "q_x", "q_0"))
+    d.c_0, d.c_e, d.c_n = (coeffs[k] for k in ("c_0", "c_e", "c_n"))
+    d.clip_on, d.clip, d.eps_from_x0 = int(coeffs["clip"] is not None), float(coeffs["clip"] or 0.0), int(coeffs["eps_from_x0"])
+    d.dtype = _DT[tokens.dtype]
+    _run(lib.aa_cfg_ddim_step_tokens, C.byref(d), _stream(latents))

@@ -18,11 +18,29 @@ import numpy as np
 import torch
 
 from . import ops
-from .schedulers import DPMSolverMultistepScheduler
+from .schedulers import DDIMScheduler, DPMSolverMultistepScheduler
 
 
 class TextToVideoSDPipelineOutput(SimpleNamespace):
     pass
+
+
+def _variance_noise(latents, generator):
+    """The noise of one stochastic (eta > 0) scheduler step: fp32, drawn in the shape the reference hands the scheduler,
+    [clips*frames, C, h, w] (reference models/pipeline.py:187-189), on the latents' device.  A generator living on another device
+    draws there and the result is moved, as diffusers' randn_tensor does."""
+    b, c, f, h, w = latents.shape
+    dev = latents.device
+    gdev = generator.device if generator is not None else dev
+    if gdev.type == dev.type:
+        return torch.randn((b * f, c, h, w), generator=generator, device=dev, dtype=torch.float32)
+    return torch.randn((b * f, c, h, w), generator=generator, device=gdev, dtype=torch.float32).to(dev)
+
+
+def _latent_layout(flat, latents):
+    """[clips*frames, C, h, w] -> the latents' [clips, C, frames, h, w]."""
+    b, c, f, h, w = latents.shape
+    return flat.reshape(b, f, c, h, w).permute(0, 2, 1, 3, 4).contiguous()
 
 
 def tensor_to_vae_latent(t, vae):
@@ -31,6 +49,17 @@ def tensor_to_vae_latent(t, vae):
     lat = vae.encode(t.reshape((b * f,) + tuple(t.shape[2:]))).latent_dist.mode()
     lat = lat.reshape((b, f) + tuple(lat.shape[1:])).permute(0, 2, 1, 3, 4)
     return lat * 0.18215
+
+
+def DDPM_forward(x0, step, num_frames, scheduler, generator=None):
+    """reference utils/common.py:22-30 (what app.py:91 starts from): x0 repeated over frames and noised with
+    prod(scheduler.alphas[t:]), t = scheduler.timesteps[-1]; needs a scheduler with `alphas` (DDIMScheduler).  `step` is
+    unused, as in the reference; returns (xt, None)."""
+    t = int(scheduler.timesteps[-1])
+    xt = x0.repeat(1, 1, num_frames, 1, 1) if x0.shape[2] == 1 else x0
+    eps = torch.randn(xt.shape, dtype=xt.dtype, device=xt.device, generator=generator)
+    alpha_vec = torch.prod(scheduler.alphas[t:]).to(device=xt.device, dtype=xt.dtype)
+    return torch.sqrt(alpha_vec) * xt + torch.sqrt(1 - alpha_vec) * eps, None
 
 
 def DDPM_forward_timesteps(x0, step, num_frames, scheduler, generator=None):
@@ -68,9 +97,12 @@ class LatentToVideoPipeline:
         self.vae_scale_factor = 2 ** (len(vae.config.block_out_channels) - 1) if vae is not None else 8
 
     @classmethod
-    def from_pretrained(cls, path, text_encoder=None, vae=None, unet=None, tokenizer=None, scheduler=None, **_):
+    def from_pretrained(cls, path, text_encoder=None, vae=None, unet=None, tokenizer=None, scheduler=None,
+                        scheduler_from_config=False, **_):
         """diffusers directory layout (reference train.py:799-804).  Components passed by the caller
-        are used as they are; the scheduler is rebuilt from `scheduler/scheduler_config.json`."""
+        are used as they are; the scheduler is rebuilt from `scheduler/scheduler_config.json`: as DPM-Solver++ (what the
+        reference's train / eval path installs over it, train.py:806-808), or with `scheduler_from_config=True` as the class
+        the file names when that is `DDIMScheduler` (what the reference's app samples with)."""
         from .unet3d import UNet3DConditionModel
         from .vae import AutoencoderKL
         if unet is None:
@@ -80,7 +112,8 @@ class LatentToVideoPipeline:
         if scheduler is None:
             cfg_path = os.path.join(path, "scheduler", "scheduler_config.json")
             cfg = json.load(open(cfg_path)) if os.path.exists(cfg_path) else {}
-            scheduler = DPMSolverMultistepScheduler.from_config(cfg)
+            ddim = scheduler_from_config and cfg.get("_class_name") == "DDIMScheduler"
+            scheduler = (DDIMScheduler if ddim else DPMSolverMultistepScheduler).from_config(cfg)
         if tokenizer is None or text_encoder is None:
             try:                   # the tokenizer is transformers' (host-side string processing), the text tower is clip.py
                 from transformers import CLIPTokenizer
@@ -158,25 +191,27 @@ class LatentToVideoPipeline:
 
     # ------------------------------------------------------------------ denoising
     def denoise(self, latents, prompt_embeds, condition_latent, mask, motion, timesteps, guidance_scale,
-                callback=None, callback_steps=1):
+                callback=None, callback_steps=1, eta=0.0, generator=None):
         """The hot loop (reference pipeline.py:163-198).  `prompt_embeds` already holds [uncond; text]
         when guidance is on.  Latents are kept in fp32.
 
-        With the DPM-Solver++ scheduler one step is exactly two device submissions: the UNet session (a hipGraph replay
-        holding timestep embedding + input packing + the whole forward when graphs are enabled) and the fused
+        With the DPM-Solver++ or the DDIM scheduler one step is exactly two device submissions: the UNet session (a hipGraph
+        replay holding timestep embedding + input packing + the whole forward when graphs are enabled) and the fused
         guidance + solver kernel, which reads the UNet's token-layout output, updates the fp32 latents in place - they ARE
-        the session's `sample` input, duplicated for guidance by the packing kernel - and deposits the next timestep."""
+        the session's `sample` input, duplicated for guidance by the packing kernel - and deposits the next timestep.
+        `eta` / `generator` reach the scheduler as in the reference (pipeline.py:156,189): DDIM with eta > 0 adds one
+        torch.randn per step, DPM-Solver++ takes neither."""
         cfg = guidance_scale > 1.0
         sched = self.scheduler
         unet = self.unet
-        if not (isinstance(sched, DPMSolverMultistepScheduler) and hasattr(unet, "session")):
+        if not (isinstance(sched, (DPMSolverMultistepScheduler, DDIMScheduler)) and hasattr(unet, "session")):
             return self._denoise_generic(latents, prompt_embeds, condition_latent, mask, motion, timesteps, guidance_scale,
-                                         callback, callback_steps)
+                                         callback, callback_steps, eta, generator)
         dev = latents.device
         b0, _, frames, h, w = latents.shape
         if cfg and self.guidance_group is not None:
             return self._denoise_guidance_parallel(latents, prompt_embeds, condition_latent, mask, motion, timesteps,
-                                                   guidance_scale, callback, callback_steps)
+                                                   guidance_scale, callback, callback_steps, eta, generator)
         b = 2 * b0 if cfg else b0
         use_mask = bool(unet.motion_mask and mask is not None)
         has_motion = bool(unet.motion_strength and motion is not None)
@@ -192,6 +227,13 @@ class LatentToVideoPipeline:
         sess.load(sample=latents, cond=condition_latent, mask=mask if use_mask else None, text=prompt_embeds, motion=mot,
                   t=torch.full((b,), float(ts[0]) if ts else 0.0, dtype=torch.float32, device=dev))
         x = sess.inputs["sample"]                               # fp32 [b0,C,T,h,w]: updated in place by the solver kernel
+        if isinstance(sched, DDIMScheduler):
+            for i, t in enumerate(ts):
+                self._ddim_step(sess.run(), x, guidance_scale if cfg else None, t, eta, generator, sess.inputs["t"],
+                                float(ts[i + 1]) if i + 1 < len(ts) else float(t))
+                if callback is not None and i % callback_steps == 0:
+                    callback(i, t, x)
+            return x.clone()
         x0_prev = torch.zeros_like(x)
         for i, t in enumerate(ts):
             eps = sess.run()                                    # tokens [b*(T+1)*h*w, 8], columns [0, out_channels) valid (row pitch = stride(0))
@@ -202,8 +244,17 @@ class LatentToVideoPipeline:
                 callback(i, t, x)
         return x.clone()
 
+    def _ddim_step(self, tokens, x, guidance, t, eta, generator, next_t, next_t_value):
+        """One fused guidance + DDIM update of the fp32 latents `x` from the UNet's token-layout output.  eta > 0 draws the
+        step's variance noise first (one torch.randn + the relayout into the latents' order; eta = 0 launches nothing else)."""
+        sched = self.scheduler
+        k = sched.coefficients(sched.index_for_timestep(t), eta)
+        noise = _latent_layout(_variance_noise(x, generator), x) if eta > 0 else None
+        ops.cfg_ddim_step_tokens(tokens, x, None, guidance, k, noise=noise if k["c_n"] != 0.0 else None,
+                                 next_t=next_t, next_t_value=next_t_value)
+
     def _denoise_guidance_parallel(self, latents, prompt_embeds, condition_latent, mask, motion, timesteps, guidance_scale,
-                                   callback=None, callback_steps=1):
+                                   callback=None, callback_steps=1, eta=0.0, generator=None):
         """Latency mode: this rank runs ONE half of the guidance batch (role 0: unconditional context = first half of
         `prompt_embeds`, role 1: the text half), the pair exchanges the UNet outputs with one all-gather per step (RCCL over
         xGMI; 0.56 MB per rank at 16x64x64) and both ranks apply the identical guidance + solver update to their copy of the
@@ -228,6 +279,12 @@ class LatentToVideoPipeline:
         for i, t in enumerate(ts):
             # (the UNet's token matrix is padded to 8 columns: only conv_out's channels travel - 0.28 MB per rank at 16x64x64)
             eps = D.all_gather_cat(sess.run()[:, :unet.conv_out.out_channels], group)          # [uncond clips | text clips], the layout the solver kernel reads
+            if isinstance(sched, DDIMScheduler):                 # (eta > 0: both ranks must hold generators in the same state)
+                self._ddim_step(eps, x, guidance_scale, t, eta, generator, sess.inputs["t"],
+                                float(ts[i + 1]) if i + 1 < len(ts) else float(t))
+                if callback is not None and i % callback_steps == 0:
+                    callback(i, t, x)
+                continue
             k = sched.coefficients(sched.index_for_timestep(t), i > 0)
             ops.cfg_dpm_step_tokens(eps, x, x0_prev, None, guidance_scale, k,
                                     next_t=sess.inputs["t"], next_t_value=float(ts[i + 1]) if i + 1 < len(ts) else float(t))
@@ -236,12 +293,21 @@ class LatentToVideoPipeline:
         return x.clone()
 
     def _denoise_generic(self, latents, prompt_embeds, condition_latent, mask, motion, timesteps, guidance_scale,
-                         callback=None, callback_steps=1):
+                         callback=None, callback_steps=1, eta=0.0, generator=None):
         """Any scheduler with a diffusers-style `step()`: the UNet through its module `forward`, guidance and the update as
-        torch expressions (the reference's own sequence, pipeline.py:165-192)."""
+        torch expressions (the reference's own sequence, pipeline.py:165-192).  `eta` / `generator` go to a `step()` that
+        names them (diffusers' prepare_extra_step_kwargs, pipeline.py:156); DDIM's variance noise is drawn here exactly as
+        the fused loop draws it, so both consume the generator alike."""
+        import inspect
         cfg = guidance_scale > 1.0
         dt = self.unet.dtype
         sched = self.scheduler
+        accepted = set(inspect.signature(sched.step).parameters)
+        extra = {}
+        if "eta" in accepted:
+            extra["eta"] = eta
+        if "generator" in accepted and not isinstance(sched, DDIMScheduler):
+            extra["generator"] = generator
         x = latents.float().contiguous()
         cond = torch.cat([condition_latent, condition_latent]) if cfg else condition_latent     # :160-161
         for i, t in enumerate(timesteps):
@@ -252,8 +318,10 @@ class LatentToVideoPipeline:
             e_u, e_t = (eps[: x.shape[0]], eps[x.shape[0]:]) if cfg else (eps, eps)
             e = e_u.float() + guidance_scale * (e_t.float() - e_u.float()) if cfg else eps.float()
             b, c, f, h, w = x.shape
+            if isinstance(sched, DDIMScheduler) and eta > 0:
+                extra["variance_noise"] = _variance_noise(x, generator)
             flat = sched.step(e.permute(0, 2, 1, 3, 4).reshape(b * f, c, h, w), t,
-                              x.permute(0, 2, 1, 3, 4).reshape(b * f, c, h, w)).prev_sample
+                              x.permute(0, 2, 1, 3, 4).reshape(b * f, c, h, w), **extra).prev_sample
             x = flat.reshape(b, f, c, h, w).permute(0, 2, 1, 3, 4).contiguous()
             if callback is not None and i % callback_steps == 0:
                 callback(i, t, x)
@@ -277,7 +345,7 @@ class LatentToVideoPipeline:
         if timesteps is None:
             timesteps = self.scheduler.timesteps
         x = self.denoise(latents, prompt_embeds, condition_latent, mask, motion, [int(t) for t in timesteps],
-                         guidance_scale, callback, callback_steps)
+                         guidance_scale, callback, callback_steps, eta=eta, generator=generator)
         latents = x.to(self.unet.dtype)
         if self.vae is None or output_type == "latent":
             video = None

@@ -8,6 +8,9 @@ dpmsolver++, order 2, midpoint, epsilon prediction, lower_order_final; SURVEY.md
 The schedule (timesteps, sigmas) and the per-step scalar coefficients are host float64 math; the
 tensor update itself is either the torch expression of `step()` (API parity with diffusers) or the
 fused HIP kernel `aa_cfg_dpm_step` fed by `coefficients()` (what the pipeline uses).
+
+`DDIMScheduler` is the scheduler the checkpoints themselves ship and the reference's app samples with; same split
+(host float64 scalars, torch `step()` or the fused kernel `aa_cfg_ddim_step_tokens`).
 """
 from __future__ import annotations
 
@@ -145,6 +148,122 @@ class DPMSolverMultistepScheduler:
         self._step_index += 1
         prev = prev.to(sample.dtype)
         return SchedulerOutput(prev_sample=prev) if return_dict else (prev,)
+
+
+class DDIMScheduler:
+    """diffusers==0.24.0 DDIMScheduler, restated from memory like the rest of this file (diffusers is not a dependency): the
+    scheduler the checkpoints of this model family carry in `scheduler/scheduler_config.json` and the one the reference's app
+    samples with (reference app.py:64-113, start latents from utils/common.py:22-30 which reads `scheduler.alphas`).
+
+    Schedule and per-step scalars are host float64 math; the tensor update is either the torch expression of `step()` (fp32,
+    API parity with diffusers) or the fused HIP kernel `aa_cfg_ddim_step_tokens` fed by `coefficients()`.  Dynamic
+    thresholding and zero-SNR beta rescaling are not implemented.  The argument defaults are the values those checkpoints
+    ship (scaled_linear 0.00085-0.012, no clipping, set_alpha_to_one=False, steps_offset=1), like the sibling classes, not
+    diffusers' own; a `scheduler_config.json` written by diffusers names every key, so `from_config` is unaffected."""
+    order = 1
+
+    def __init__(self, num_train_timesteps=1000, beta_start=0.00085, beta_end=0.012, beta_schedule="scaled_linear",
+                 clip_sample=False, set_alpha_to_one=False, steps_offset=1, prediction_type="epsilon", thresholding=False,
+                 clip_sample_range=1.0, timestep_spacing="leading", rescale_betas_zero_snr=False, **_):
+        if thresholding or rescale_betas_zero_snr:
+            raise NotImplementedError("DDIMScheduler: thresholding / rescale_betas_zero_snr are not implemented")
+        if prediction_type not in ("epsilon", "v_prediction", "sample"):
+            raise ValueError(f"prediction_type {prediction_type!r}: epsilon, v_prediction or sample")
+        if timestep_spacing not in ("leading", "trailing", "linspace"):
+            raise ValueError(f"timestep_spacing {timestep_spacing!r}: leading, trailing or linspace")
+        self.config = SimpleNamespace(num_train_timesteps=num_train_timesteps, beta_start=beta_start, beta_end=beta_end,
+                                      beta_schedule=beta_schedule, clip_sample=clip_sample, set_alpha_to_one=set_alpha_to_one,
+                                      steps_offset=steps_offset, prediction_type=prediction_type, thresholding=thresholding,
+                                      clip_sample_range=clip_sample_range, timestep_spacing=timestep_spacing,
+                                      rescale_betas_zero_snr=rescale_betas_zero_snr)
+        betas = _betas(num_train_timesteps, beta_start, beta_end, beta_schedule)
+        self._acp = np.cumprod(1.0 - betas)
+        self.betas = torch.from_numpy(betas)
+        self.alphas = 1.0 - self.betas
+        self.alphas_cumprod = torch.from_numpy(self._acp)
+        self.final_alpha_cumprod = 1.0 if set_alpha_to_one else float(self._acp[0])
+        self.init_noise_sigma = 1.0
+        self.num_inference_steps = None
+        self.timesteps = torch.from_numpy(np.arange(0, num_train_timesteps)[::-1].copy().astype(np.int64))
+        self._ts = [int(t) for t in self.timesteps]
+
+    @classmethod
+    def from_config(cls, config, **overrides):
+        cfg = dict(vars(config)) if isinstance(config, SimpleNamespace) else dict(config)
+        cfg.update(overrides)
+        return cls(**{k: v for k, v in cfg.items() if not k.startswith("_")})
+
+    def set_timesteps(self, num_inference_steps, device=None):
+        c, N, n = self.config, self.config.num_train_timesteps, int(num_inference_steps)
+        if not 0 < n <= N:
+            raise ValueError(f"num_inference_steps = {num_inference_steps} must lie in [1, {N}]")
+        if c.timestep_spacing == "linspace":
+            ts = np.linspace(0, N - 1, n).round()[::-1].copy().astype(np.int64)
+        elif c.timestep_spacing == "leading":
+            ts = (np.arange(0, n) * (N // n)).round()[::-1].copy().astype(np.int64) + c.steps_offset
+        else:
+            ts = np.round(np.arange(N, 0, -N / n)).astype(np.int64) - 1
+        self.timesteps = torch.from_numpy(ts).to(device) if device is not None else torch.from_numpy(ts)
+        self._ts = [int(t) for t in ts]
+        self.num_inference_steps = n
+
+    def scale_model_input(self, sample, timestep=None):
+        return sample
+
+    def add_noise(self, original_samples, noise, timesteps):
+        acp = self.alphas_cumprod.to(original_samples.device)[torch.as_tensor(timesteps).to(original_samples.device).long()]
+        shape = (-1,) + (1,) * (original_samples.dim() - 1)
+        a = acp.sqrt().reshape(shape).to(original_samples.dtype)
+        s = (1 - acp).sqrt().reshape(shape).to(original_samples.dtype)
+        return a * original_samples + s * noise
+
+    def index_for_timestep(self, timestep):
+        return self._ts.index(int(timestep))
+
+    # ---- scalar part of one step (shared by `step` and the fused kernel) -------------------------
+    def _coefficients_at(self, t: int, eta: float, use_clipped_model_output: bool):
+        c, N = self.config, self.config.num_train_timesteps
+        if self.num_inference_steps is None:
+            raise ValueError("call set_timesteps() before stepping")
+        t_prev = t - N // self.num_inference_steps
+        a_t = float(self._acp[t])
+        a_prev = float(self._acp[t_prev]) if t_prev >= 0 else self.final_alpha_cumprod
+        b_t = 1.0 - a_t
+        sa, sb = math.sqrt(a_t), math.sqrt(b_t)
+        if c.prediction_type == "epsilon":
+            a_x, a_m, e_x, e_m = 1.0 / sa, -sb / sa, 0.0, 1.0
+        elif c.prediction_type == "sample":
+            a_x, a_m, e_x, e_m = 0.0, 1.0, 1.0 / sb, -sa / sb
+        else:
+            a_x, a_m, e_x, e_m = sa, -sb, sb, sa
+        sigma = float(eta) * math.sqrt((1.0 - a_prev) / (1.0 - a_t) * (1.0 - a_t / a_prev))
+        return dict(a_x=a_x, a_m=a_m, e_x=e_x, e_m=e_m, q_x=1.0 / sb, q_0=-sa / sb,
+                    clip=float(c.clip_sample_range) if c.clip_sample else None, eps_from_x0=bool(use_clipped_model_output),
+                    c_0=math.sqrt(a_prev), c_e=math.sqrt(1.0 - a_prev - sigma * sigma), c_n=sigma)
+
+    def coefficients(self, step_index: int, eta: float = 0.0, use_clipped_model_output: bool = False):
+        """x0 = a_x*x + a_m*m (clamped to +-clip unless clip is None);  eps = e_x*x + e_m*m, or q_x*x + q_0*x0 when eps_from_x0;
+        x' = c_0*x0 + c_e*eps + c_n*noise.  Returns dict(a_x, a_m, e_x, e_m, q_x, q_0, clip, eps_from_x0, c_0, c_e, c_n)."""
+        return self._coefficients_at(self._ts[step_index], eta, use_clipped_model_output)
+
+    def step(self, model_output, timestep, sample, eta=0.0, use_clipped_model_output=False, generator=None,
+             variance_noise=None, return_dict=True):
+        """diffusers-compatible tensor update (torch ops, fp32 arithmetic)."""
+        k = self._coefficients_at(int(timestep), eta, use_clipped_model_output)
+        x, m = sample.float(), model_output.float()
+        x0 = k["a_x"] * x + k["a_m"] * m
+        if k["clip"] is not None:
+            x0 = x0.clamp(-k["clip"], k["clip"])
+        eps = k["q_x"] * x + k["q_0"] * x0 if k["eps_from_x0"] else k["e_x"] * x + k["e_m"] * m
+        prev = k["c_0"] * x0 + k["c_e"] * eps
+        if eta > 0:                                         # (diffusers draws whenever eta > 0, also where sigma_t comes out 0)
+            if variance_noise is not None and generator is not None:
+                raise ValueError("pass either `generator` or `variance_noise`, not both")
+            if variance_noise is None:
+                variance_noise = torch.randn(model_output.shape, generator=generator, device=model_output.device, dtype=torch.float32)
+            prev = prev + k["c_n"] * variance_noise.float()
+        prev, x0 = prev.to(sample.dtype), x0.to(sample.dtype)
+        return SchedulerOutput(prev_sample=prev, pred_original_sample=x0) if return_dict else (prev,)
 
 
 class EulerDiscreteScheduler:

@@ -583,6 +583,41 @@ typedef struct AaEulerStepTok {
 
 int aa_cfg_euler_step_tokens(const AaEulerStepTok* d, void* stream);
 
+/* aa_cfg_ddim_step_tokens: classifier-free guidance + DDIMScheduler.step (diffusers 0.24; the scheduler the checkpoints of this
+ * model family ship and the reference's app samples with, app.py:64-113) reading the UNet output where the UNet left it - the
+ * token matrix [2*clips or clips][frames+1][hw][ld] with frame 0 (the condition frame) skipped and, under guidance, the
+ * unconditional clips first, exactly as aa_cfg_dpm_step_tokens reads it:
+ *   m  = m_uncond + guidance * (m_text - m_uncond)
+ *   x0 = a_x * x + a_m * m;   clip_on: x0 = clamp(x0, -clip, clip)              (pred_original_sample, clip_sample)
+ *   e  = e_x * x + e_m * m,   or  q_x * x + q_0 * x0  when eps_from_x0           (use_clipped_model_output)
+ *   x' = c_0 * x0 + c_e * e + c_n * noise                                        (c_n = sigma_t(eta); 0: no noise read)
+ * The caller folds the prediction type (epsilon / sample / v_prediction), alpha_bar_t, alpha_bar_prev and eta into the
+ * scalars (schedulers.DDIMScheduler.coefficients, float64).  All arithmetic is fp32.  Updates the fp32 latents
+ * [clips][channels][frames][hw] in place, optionally writes their storage-dtype copy and the next timestep value(s) for
+ * aa_timestep_embedding.  `noise` is fp32 in the latents' layout and required exactly when c_n != 0. */
+typedef struct AaDdimStepTok {
+    const void* tokens;
+    void* latents;            /* fp32, updated in place */
+    void* latents_lp;         /* storage dtype copy of the new latents, may be NULL */
+    const float* noise;       /* fp32 variance noise; read only when c_n != 0 (NULL then: AA_E_SHAPE) */
+    float* next_t;            /* device array receiving `next_t_value` (next_t_count <= 256 entries), may be NULL */
+    int32_t next_t_count;
+    float next_t_value;
+    int32_t clips, channels, frames, hw;
+    int32_t ld;               /* row pitch of the token matrix in elements (>= channels) */
+    int32_t guidance_on;
+    float guidance;
+    float a_x, a_m;
+    int32_t clip_on;
+    float clip;
+    int32_t eps_from_x0;
+    float e_x, e_m, q_x, q_0;
+    float c_0, c_e, c_n;
+    int32_t dtype;
+} AaDdimStepTok;
+
+int aa_cfg_ddim_step_tokens(const AaDdimStepTok* d, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
