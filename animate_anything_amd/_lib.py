@@ -163,10 +163,22 @@ class AaDdimStepTok(C.Structure):
     ]
 
 
+class AaUnipcStepTok(C.Structure):
+    _fields_ = [
+        ("tokens", C.c_void_p), ("latents", C.c_void_p), ("latents_lp", C.c_void_p), ("last_sample", C.c_void_p),
+        ("hist1", C.c_void_p), ("hist2", C.c_void_p), ("hist3", C.c_void_p), ("next_t", C.c_void_p),
+        ("next_t_count", C.c_int32), ("next_t_value", C.c_float),
+        ("clips", C.c_int32), ("channels", C.c_int32), ("frames", C.c_int32), ("hw", C.c_int32), ("ld", C.c_int32),
+        ("guidance_on", C.c_int32), ("guidance", C.c_float), ("a_x", C.c_float), ("a_m", C.c_float),
+        ("corr_on", C.c_int32), ("q_l", C.c_float), ("q_1", C.c_float), ("q_2", C.c_float), ("q_3", C.c_float), ("q_n", C.c_float),
+        ("p_x", C.c_float), ("p_0", C.c_float), ("p_1", C.c_float), ("p_2", C.c_float), ("dtype", C.c_int32),
+    ]
+
+
 SYMBOLS = ("aa_version", "aa_last_error", "aa_set_tile_override", "aa_conv_gemm_tile_info", "aa_conv_gemm_tile_ok", "aa_conv_gemm_workspace", "aa_conv_gemm", "aa_conv_gemm_launch_count", "aa_conv_gemm_row_stats_parts", "aa_conv_gemm_row_coef_ok", "aa_conv_gemm_tickets", "aa_conv_gemm_reduce_launches", "aa_conv_gemm_tile_flags", "aa_ln_finalize", "aa_groupnorm_workspace", "aa_groupnorm", "aa_groupnorm_coef", "aa_set_groupnorm_two_pass", "aa_groupnorm_plan",
            "aa_layernorm", "aa_attention", "aa_seq_self_attention_ok", "aa_seq_self_attention", "aa_ff_fused_ok", "aa_ff_fused", "aa_linear_rows_ok", "aa_linear_rows", "aa_quant_rows_fp8", "aa_linear_fp8", "aa_softmax_rows", "aa_cfg_dpm_step",
            "aa_timestep_embedding", "aa_pack_latents", "aa_cfg_dpm_step_tokens",
-           "aa_blend", "aa_pack_frames", "aa_cfg_euler_step_tokens", "aa_cfg_ddim_step_tokens")
+           "aa_blend", "aa_pack_frames", "aa_cfg_euler_step_tokens", "aa_cfg_ddim_step_tokens", "aa_cfg_unipc_step_tokens")
 
 DEFAULT_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libaa_mi355.so")
 
@@ -229,6 +241,7 @@ def bind(path: str) -> C.CDLL:
     lib.aa_pack_frames.argtypes = [C.POINTER(AaPackFrames), C.c_void_p]
     lib.aa_cfg_euler_step_tokens.argtypes = [C.POINTER(AaEulerStepTok), C.c_void_p]
     lib.aa_cfg_ddim_step_tokens.argtypes = [C.POINTER(AaDdimStepTok), C.c_void_p]
+    lib.aa_cfg_unipc_step_tokens.argtypes = [C.POINTER(AaUnipcStepTok), C.c_void_p]
     for s in SYMBOLS[5:]:
         if s not in ("aa_groupnorm_workspace", "aa_conv_gemm_workspace"):
             getattr(lib, s).restype = C.c_int

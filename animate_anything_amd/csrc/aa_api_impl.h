@@ -1078,5 +1078,27 @@ int aa_cfg_ddim_step_tokens(const AaDdimStepTok* d, void* stream) {
     return finish("cfg_ddim_step_tokens");
 }
 
+int aa_cfg_unipc_step_tokens(const AaUnipcStepTok* d, void* stream) {
+    using namespace aa;
+    if (!d || !d->tokens || !d->latents || !d->last_sample) return fail(AA_E_SHAPE, "cfg_unipc_step_tokens: null operand");
+    if (d->clips <= 0 || d->channels <= 0 || d->frames <= 0 || d->hw <= 0 || d->ld < d->channels || d->next_t_count < 0 || d->next_t_count > 256)
+        return fail(AA_E_SHAPE, "cfg_unipc_step_tokens: bad geometry");
+    if (((d->q_1 != 0.0f || d->p_1 != 0.0f) && !d->hist1) || ((d->q_2 != 0.0f || d->p_2 != 0.0f) && !d->hist2) || (d->q_3 != 0.0f && !d->hist3))
+        return fail(AA_E_SHAPE, "cfg_unipc_step_tokens: a non-zero history coefficient needs its history buffer");
+    const int64_t n = (int64_t)d->clips * d->channels * d->frames * d->hw;
+    const char* buf[5] = {(const char*)d->latents, (const char*)d->last_sample, (const char*)d->hist1, (const char*)d->hist2, (const char*)d->hist3};
+    for (int i = 0; i < 5; ++i)
+        for (int j = i + 1; j < 5; ++j)
+            if (buf[i] && buf[j] && buf[i] < buf[j] + n * 4 && buf[j] < buf[i] + n * 4)
+                return fail(AA_E_SHAPE, "cfg_unipc_step_tokens: latents, last_sample and the history buffers must not overlap");
+    int64_t blocks = (n + 255) / 256;
+    if (blocks > 2048) blocks = 2048;
+    const dim3 grid((unsigned)blocks), block(256);
+    if (d->dtype == AA_F16) AA_LAUNCH((cfg_unipc_step_tok_kernel<f16_t>), grid, block, 0, stream, *d);
+    else if (d->dtype == AA_BF16) AA_LAUNCH((cfg_unipc_step_tok_kernel<bf16_t>), grid, block, 0, stream, *d);
+    else return fail(AA_E_DTYPE, "cfg_unipc_step_tokens: unsupported dtype %d", d->dtype);
+    return finish("cfg_unipc_step_tokens");
+}
+
 }  // extern "C"
 #endif  // AA_TU_TILES_ONLY

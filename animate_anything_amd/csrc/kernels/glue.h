@@ -6,6 +6,7 @@
 //  * cfg_dpm_step_tok_kernel aa_cfg_dpm_step reading the UNet's token-layout output (frame 0 dropped, :522) and writing
 //                            the next UNet input
 //  * cfg_ddim_step_tok_kernel the same for DDIMScheduler.step (the scheduler the checkpoints ship; reference app.py:64-113)
+//  * cfg_unipc_step_tok_kernel the same for UniPCMultistepScheduler.step: the corrector of the step before + this step's predictor
 #pragma once
 #include "dev.h"
 #include "aa_mi355.h"
@@ -112,6 +113,51 @@ __global__ void __launch_bounds__(256) cfg_ddim_step_tok_kernel(const AaDdimStep
         float nx = p.c_0 * x0 + p.c_e * e;
         if (p.c_n != 0.0f) nx += p.c_n * p.noise[i];
         x[i] = nx;
+        if (p.latents_lp) reinterpret_cast<T*>(p.latents_lp)[i] = (T)nx;
+    }
+}
+
+// guidance + one UniPC step (corrector of the step before, then the predictor) with the scalars folded by the caller
+// (aa_mi355.h AaUnipcStepTok); token addressing of cfg_ddim_step_tok_kernel.  fp32 throughout.  Every buffer is read and written
+// at element i by the thread that owns i alone, and m goes into the oldest history buffer after that thread has read it: the
+// entry point refuses overlapping buffers and a null one whose coefficient is not zero.
+template <typename T>
+__global__ void __launch_bounds__(256) cfg_unipc_step_tok_kernel(const AaUnipcStepTok p) {
+    const T* tok = reinterpret_cast<const T*>(p.tokens);
+    float* x = reinterpret_cast<float*>(p.latents);
+    float* m_out = p.hist3 ? p.hist3 : p.hist2 ? p.hist2 : p.hist1;
+    const int T1 = p.frames + 1;
+    const int64_t n = (int64_t)p.clips * p.channels * p.frames * p.hw;
+    if (p.next_t && blockIdx.x == 0 && threadIdx.x < p.next_t_count) p.next_t[threadIdx.x] = p.next_t_value;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+        const int pix = (int)(i % p.hw);
+        int64_t r = i / p.hw;
+        const int f = (int)(r % p.frames); r /= p.frames;
+        const int c = (int)(r % p.channels);
+        const int b = (int)(r / p.channels);
+        const int64_t tok_u = ((int64_t)b * T1 + f + 1) * p.hw + pix;                   // frame 0 of the UNet output is dropped (:522)
+        const float u = (float)tok[tok_u * p.ld + c];
+        float e = u;
+        if (p.guidance_on) {
+            const int64_t tok_t = ((int64_t)(p.clips + b) * T1 + f + 1) * p.hw + pix;   // [uncond clips | text clips] (pipeline.py:165)
+            e = u + p.guidance * ((float)tok[tok_t * p.ld + c] - u);
+        }
+        const float xi = x[i];
+        const float m = p.a_x * xi + p.a_m * e;
+        const float m1 = (p.q_1 != 0.0f || p.p_1 != 0.0f) ? p.hist1[i] : 0.0f;
+        const float m2 = (p.q_2 != 0.0f || p.p_2 != 0.0f) ? p.hist2[i] : 0.0f;
+        float xh = xi;
+        if (p.corr_on) {
+            xh = p.q_l * p.last_sample[i] + p.q_1 * m1 + p.q_n * m;
+            if (p.q_2 != 0.0f) xh += p.q_2 * m2;
+            if (p.q_3 != 0.0f) xh += p.q_3 * p.hist3[i];
+        }
+        float nx = p.p_x * xh + p.p_0 * m;
+        if (p.p_1 != 0.0f) nx += p.p_1 * m1;
+        if (p.p_2 != 0.0f) nx += p.p_2 * m2;
+        x[i] = nx;
+        p.last_sample[i] = xh;
+        if (m_out) m_out[i] = m;
         if (p.latents_lp) reinterpret_cast<T*>(p.latents_lp)[i] = (T)nx;
     }
 }

@@ -5,7 +5,8 @@
 
 Same YAML keys and dot-list overrides (`pretrained_model_path`, `validation_data.{prompt,prompt_image,mask,strength,
 num_frames,width,height,num_inference_steps,guidance_scale,fps}`, `seed`, `motion_mask`, `motion_strength`), plus
-`sampler: ddim` for the checkpoint's own DDIM scheduler in place of DPM-Solver++.
+`sampler: ddim` for the checkpoint's own DDIM scheduler or `sampler: unipc` for UniPC (the sampler for 8-12 steps) in place
+of DPM-Solver++.
 The third-party pieces the reference pulls in and that do not exist in this image are replaced by small
 equivalents: OmegaConf -> PyYAML + dot-list merge, `VaeImageProcessor.preprocess` -> PIL lanczos resize + [-1,1]
 scaling, torchvision `ToTensor`/`Resize(antialias=False)` -> torch bilinear interpolate, imageio -> PIL GIF writer.
@@ -29,7 +30,7 @@ from PIL import Image
 
 from .pipeline import (DDPM_forward_timesteps, LatentToVideoPipeline, calculate_latent_motion_score,
                        tensor_to_vae_latent)
-from .schedulers import DDIMScheduler, DDPMScheduler, DPMSolverMultistepScheduler
+from .schedulers import DDIMScheduler, DDPMScheduler, DPMSolverMultistepScheduler, UniPCMultistepScheduler
 from .unet3d import UNet3DConditionModel
 from .vae import AutoencoderKL
 
@@ -199,17 +200,25 @@ def eval(pipeline, validation_data, out_file, index, forward_t=25, preview=True,
     return precision, video_frames, video_latents
 
 
+SAMPLERS = {"dpm": DPMSolverMultistepScheduler, "ddim": DDIMScheduler, "unipc": UniPCMultistepScheduler}
+
+
+def _check_sampler(sampler):
+    if sampler not in SAMPLERS:
+        raise ValueError(f"sampler {sampler!r}: dpm (DPM-Solver++, the default), ddim or unipc")
+
+
 def batch_eval(unet, text_encoder, vae, tokenizer, scheduler_config, validation_data, output_dir, preview,
                global_step=0, iters=6, generator=None, indices=None, seed=None, lora_path=None, lora_rank=16,
                unet_lora_modules=("UNet3DConditionModel",), guidance_group=None, sampler="dpm"):
     """train.py:793-823: pipeline with DPM-Solver++ built from the checkpoint's scheduler config, `iters` samples
-    (`sampler="ddim"`: DDIM from the same config, the scheduler the reference's app keeps, app.py:65).
+    (`sampler="ddim"`: DDIM from the same config, the scheduler the reference's app keeps, app.py:65; `sampler="unipc"`: UniPC
+    from the same config).
     `indices` (clip sharding, main_eval): render only these sample indices, each with its own generator seeded
     `seed + index` (distributed.clip_seed) so that a sample does not depend on which rank renders it."""
+    _check_sampler(sampler)
     unet.eval()
-    if sampler not in ("dpm", "ddim"):
-        raise ValueError(f"sampler {sampler!r}: dpm (DPM-Solver++, the default) or ddim")
-    scheduler = (DDIMScheduler if sampler == "ddim" else DPMSolverMultistepScheduler).from_config(scheduler_config)
+    scheduler = SAMPLERS[sampler].from_config(scheduler_config)
     pipeline = LatentToVideoPipeline(vae=vae, text_encoder=text_encoder, tokenizer=tokenizer, unet=unet,
                                      scheduler=scheduler)
     pipeline.guidance_group = guidance_group              # latency mode: the guidance halves of a clip on the two GPUs of a pair
@@ -242,8 +251,7 @@ def main_eval(pretrained_model_path, validation_data, seed=None, motion_mask=Non
     Under `torchrun` (WORLD_SIZE > 1: BASELINE.json configs[2], "bs=8, 1 clip/GPU") the `iters` samples of the clip batch
     are sharded round-robin over the ranks (rank r renders samples r, r+W, ...; per-sample seed = seed + index so the
     outputs do not depend on W) and the final latents are all-gathered over RCCL (distributed.gather_clips)."""
-    if sampler not in ("dpm", "ddim"):                    # (before any model is loaded)
-        raise ValueError(f"sampler {sampler!r}: dpm (DPM-Solver++, the default) or ddim")
+    _check_sampler(sampler)                               # (before any model is loaded)
     from . import distributed as D
     rank, world, _dev = D.init()
     generator = None

@@ -16,7 +16,7 @@ import torch
 
 from . import _lib
 from ._lib import (AA_ACT_GELU, AA_ACT_NONE, AA_ACT_QUICK_GELU, AA_ACT_SILU, AA_BF16, AA_F16, AA_F32, AaAttention, AaAttnOperand,
-                   AaBlend, AaConvGemm, AaFFFused, AaLinearRows, AaLinearFp8, AaQuantRowsFp8, AaDdimStepTok, AaDpmStep, AaDpmStepTok, AaEulerStepTok, AaGroupNorm, AaPackFrames, AaPackLatents, AaSeqSelfAttn)
+                   AaBlend, AaConvGemm, AaFFFused, AaLinearRows, AaLinearFp8, AaQuantRowsFp8, AaDdimStepTok, AaDpmStep, AaDpmStepTok, AaEulerStepTok, AaGroupNorm, AaPackFrames, AaPackLatents, AaSeqSelfAttn, AaUnipcStepTok)
 
 _DT = {torch.float16: AA_F16, torch.bfloat16: AA_BF16, torch.float32: AA_F32}
 
@@ -1304,3 +1304,45 @@ def cfg_ddim_step_tokens(tokens, latents, latents_lp, guidance, coeffs, noise=No
     d.clip_on, d.clip, d.eps_from_x0 = int(coeffs["clip"] is not None), float(coeffs["clip"] or 0.0), int(coeffs["eps_from_x0"])
     d.dtype = _DT[tokens.dtype]
     _run(lib.aa_cfg_ddim_step_tokens, C.byref(d), _stream(latents))
+
+
+def cfg_unipc_step_tokens(tokens, latents, latents_lp, guidance, coeffs, last_sample, history, next_t=None, next_t_value=0.0):
+    """Fused CFG + UniPC step (corrector of the step before + predictor) reading the UNet's token-layout output
+    [(2*)clips*(T+1)*hw, ld]; latents fp32 [clips, C, T, h, w] updated in place.  `coeffs` is
+    schedulers.UniPCMultistepScheduler.coefficients(); `last_sample` (fp32, the latents' shape) receives the corrected sample;
+    `history` = (m of the previous step, of the second previous, of the third previous), fp32 in the latents' shape, an entry
+    may be None where its coefficients are zero.  The kernel writes this step's m into the last entry that is not None;
+    returns the history rotated for the next step."""
+    lib = _lib.get()
+    history = tuple(history)
+    if len(history) != 3:
+        raise RuntimeError("cfg_unipc_step_tokens: history must hold three entries (tensors or None)")
+    _check(tokens, latents, latents_lp, last_sample, *history, next_t)
+    if latents.dtype != torch.float32 or latents.dim() != 5:
+        raise RuntimeError("cfg_unipc_step_tokens: latents must be fp32 [clips, C, T, h, w]")
+    if last_sample is None or last_sample.shape != latents.shape or last_sample.dtype != torch.float32:
+        raise RuntimeError("cfg_unipc_step_tokens: last_sample must be fp32 in the latents' shape")
+    for hbuf in history:
+        if hbuf is not None and (hbuf.shape != latents.shape or hbuf.dtype != torch.float32):
+            raise RuntimeError("cfg_unipc_step_tokens: history buffers must be fp32 in the latents' shape")
+    if latents_lp is not None and (latents_lp.shape != latents.shape or latents_lp.dtype != tokens.dtype):
+        raise RuntimeError("cfg_unipc_step_tokens: latents_lp must have the latents' shape and the tokens' dtype")
+    if next_t is not None and next_t.dtype != torch.float32:
+        raise RuntimeError("cfg_unipc_step_tokens: next_t must be fp32")
+    clips, c, frames, h, w = latents.shape
+    rows = (2 if guidance is not None else 1) * clips * (frames + 1) * h * w
+    if tokens.dim() != 2 or tokens.shape[0] < rows or tokens.shape[1] < c:
+        raise RuntimeError(f"cfg_unipc_step_tokens: tokens {tuple(tokens.shape)} do not hold {rows} rows of {c} channels")
+    d = AaUnipcStepTok()
+    d.tokens, d.latents, d.latents_lp, d.last_sample = _ptr(tokens), _ptr(latents), _ptr(latents_lp), _ptr(last_sample)
+    d.hist1, d.hist2, d.hist3 = (_ptr(hbuf) for hbuf in history)
+    d.next_t, d.next_t_count, d.next_t_value = _ptr(next_t), 0 if next_t is None else next_t.numel(), float(next_t_value)
+    d.clips, d.channels, d.frames, d.hw, d.ld = clips, c, frames, h * w, tokens.stride(0)
+    d.guidance_on, d.guidance = int(guidance is not None), float(guidance or 0.0)
+    d.a_x, d.a_m, d.corr_on = coeffs["a_x"], coeffs["a_m"], int(bool(coeffs["corr_on"]))
+    d.q_l, d.q_1, d.q_2, d.q_3, d.q_n = (coeffs[k] for k in ("q_l", "q_1", "q_2", "q_3", "q_n"))
+    d.p_x, d.p_0, d.p_1, d.p_2 = (coeffs[k] for k in ("p_x", "p_0", "p_1", "p_2"))
+    d.dtype = _DT[tokens.dtype]
+    _run(lib.aa_cfg_unipc_step_tokens, C.byref(d), _stream(latents))
+    live = [hbuf for hbuf in history if hbuf is not None]
+    return tuple(live[-1:] + live[:-1]) + (None,) * (3 - len(live))

@@ -18,7 +18,7 @@ import numpy as np
 import torch
 
 from . import ops
-from .schedulers import DDIMScheduler, DPMSolverMultistepScheduler
+from .schedulers import DDIMScheduler, DPMSolverMultistepScheduler, UniPCMultistepScheduler
 
 
 class TextToVideoSDPipelineOutput(SimpleNamespace):
@@ -102,7 +102,7 @@ class LatentToVideoPipeline:
         """diffusers directory layout (reference train.py:799-804).  Components passed by the caller
         are used as they are; the scheduler is rebuilt from `scheduler/scheduler_config.json`: as DPM-Solver++ (what the
         reference's train / eval path installs over it, train.py:806-808), or with `scheduler_from_config=True` as the class
-        the file names when that is `DDIMScheduler` (what the reference's app samples with)."""
+        the file names when that is `DDIMScheduler` (what the reference's app samples with) or `UniPCMultistepScheduler`."""
         from .unet3d import UNet3DConditionModel
         from .vae import AutoencoderKL
         if unet is None:
@@ -112,8 +112,9 @@ class LatentToVideoPipeline:
         if scheduler is None:
             cfg_path = os.path.join(path, "scheduler", "scheduler_config.json")
             cfg = json.load(open(cfg_path)) if os.path.exists(cfg_path) else {}
-            ddim = scheduler_from_config and cfg.get("_class_name") == "DDIMScheduler"
-            scheduler = (DDIMScheduler if ddim else DPMSolverMultistepScheduler).from_config(cfg)
+            named = {"DDIMScheduler": DDIMScheduler, "UniPCMultistepScheduler": UniPCMultistepScheduler}
+            kind = named.get(cfg.get("_class_name"), DPMSolverMultistepScheduler) if scheduler_from_config else DPMSolverMultistepScheduler
+            scheduler = kind.from_config(cfg)
         if tokenizer is None or text_encoder is None:
             try:                   # the tokenizer is transformers' (host-side string processing), the text tower is clip.py
                 from transformers import CLIPTokenizer
@@ -195,16 +196,17 @@ class LatentToVideoPipeline:
         """The hot loop (reference pipeline.py:163-198).  `prompt_embeds` already holds [uncond; text]
         when guidance is on.  Latents are kept in fp32.
 
-        With the DPM-Solver++ or the DDIM scheduler one step is exactly two device submissions: the UNet session (a hipGraph
+        With the DPM-Solver++, the DDIM or the UniPC scheduler one step is exactly two device submissions: the UNet session (a hipGraph
         replay holding timestep embedding + input packing + the whole forward when graphs are enabled) and the fused
         guidance + solver kernel, which reads the UNet's token-layout output, updates the fp32 latents in place - they ARE
         the session's `sample` input, duplicated for guidance by the packing kernel - and deposits the next timestep.
         `eta` / `generator` reach the scheduler as in the reference (pipeline.py:156,189): DDIM with eta > 0 adds one
-        torch.randn per step, DPM-Solver++ takes neither."""
+        torch.randn per step, DPM-Solver++ and UniPC take neither.  UniPC keeps four fp32 buffers of the latents' size for
+        the length of the call (the corrected sample and three data predictions)."""
         cfg = guidance_scale > 1.0
         sched = self.scheduler
         unet = self.unet
-        if not (isinstance(sched, (DPMSolverMultistepScheduler, DDIMScheduler)) and hasattr(unet, "session")):
+        if not (isinstance(sched, (DPMSolverMultistepScheduler, DDIMScheduler, UniPCMultistepScheduler)) and hasattr(unet, "session")):
             return self._denoise_generic(latents, prompt_embeds, condition_latent, mask, motion, timesteps, guidance_scale,
                                          callback, callback_steps, eta, generator)
         dev = latents.device
@@ -234,6 +236,14 @@ class LatentToVideoPipeline:
                 if callback is not None and i % callback_steps == 0:
                     callback(i, t, x)
             return x.clone()
+        if isinstance(sched, UniPCMultistepScheduler):
+            state = self._unipc_state(x)
+            for i, t in enumerate(ts):
+                self._unipc_step(sess.run(), x, guidance_scale if cfg else None, t, i, state, sess.inputs["t"],
+                                 float(ts[i + 1]) if i + 1 < len(ts) else float(t))
+                if callback is not None and i % callback_steps == 0:
+                    callback(i, t, x)
+            return x.clone()
         x0_prev = torch.zeros_like(x)
         for i, t in enumerate(ts):
             eps = sess.run()                                    # tokens [b*(T+1)*h*w, 8], columns [0, out_channels) valid (row pitch = stride(0))
@@ -252,6 +262,20 @@ class LatentToVideoPipeline:
         noise = _latent_layout(_variance_noise(x, generator), x) if eta > 0 else None
         ops.cfg_ddim_step_tokens(tokens, x, None, guidance, k, noise=noise if k["c_n"] != 0.0 else None,
                                  next_t=next_t, next_t_value=next_t_value)
+
+    @staticmethod
+    def _unipc_state(x):
+        """The four fp32 buffers a UniPC run keeps next to the latents: [corrected sample, m of the previous step, of the second
+        previous, of the third previous] (zeroed: a coefficient of zero must not meet a NaN)."""
+        return [torch.zeros_like(x) for _ in range(4)]
+
+    def _unipc_step(self, tokens, x, guidance, t, steps_done, state, next_t, next_t_value):
+        """One fused guidance + UniPC step (corrector of the step before + predictor) of the fp32 latents `x` from the UNet's
+        token-layout output; `steps_done` counts the steps of this run before it.  Rotates the history in `state`."""
+        sched = self.scheduler
+        k = sched.coefficients(sched.index_for_timestep(t), steps_done)
+        state[1:] = ops.cfg_unipc_step_tokens(tokens, x, None, guidance, k, state[0], state[1:],
+                                              next_t=next_t, next_t_value=next_t_value)
 
     def _denoise_guidance_parallel(self, latents, prompt_embeds, condition_latent, mask, motion, timesteps, guidance_scale,
                                    callback=None, callback_steps=1, eta=0.0, generator=None):
@@ -276,12 +300,19 @@ class LatentToVideoPipeline:
                   t=torch.full((b0,), float(ts[0]) if ts else 0.0, dtype=torch.float32, device=dev))
         x = sess.inputs["sample"]
         x0_prev = torch.zeros_like(x)
+        state = self._unipc_state(x) if isinstance(sched, UniPCMultistepScheduler) else None
         for i, t in enumerate(ts):
             # (the UNet's token matrix is padded to 8 columns: only conv_out's channels travel - 0.28 MB per rank at 16x64x64)
             eps = D.all_gather_cat(sess.run()[:, :unet.conv_out.out_channels], group)          # [uncond clips | text clips], the layout the solver kernel reads
             if isinstance(sched, DDIMScheduler):                 # (eta > 0: both ranks must hold generators in the same state)
                 self._ddim_step(eps, x, guidance_scale, t, eta, generator, sess.inputs["t"],
                                 float(ts[i + 1]) if i + 1 < len(ts) else float(t))
+                if callback is not None and i % callback_steps == 0:
+                    callback(i, t, x)
+                continue
+            if state is not None:
+                self._unipc_step(eps, x, guidance_scale, t, i, state, sess.inputs["t"],
+                                 float(ts[i + 1]) if i + 1 < len(ts) else float(t))
                 if callback is not None and i % callback_steps == 0:
                     callback(i, t, x)
                 continue

@@ -11,6 +11,9 @@ fused HIP kernel `aa_cfg_dpm_step` fed by `coefficients()` (what the pipeline us
 
 `DDIMScheduler` is the scheduler the checkpoints themselves ship and the reference's app samples with; same split
 (host float64 scalars, torch `step()` or the fused kernel `aa_cfg_ddim_step_tokens`).
+
+`UniPCMultistepScheduler` is the sampler for 8-12 steps: DPM-Solver++'s multistep predictor plus a corrector that costs no
+extra UNet call; same split, fused kernel `aa_cfg_unipc_step_tokens`.
 """
 from __future__ import annotations
 
@@ -264,6 +267,203 @@ class DDIMScheduler:
             prev = prev + k["c_n"] * variance_noise.float()
         prev, x0 = prev.to(sample.dtype), x0.to(sample.dtype)
         return SchedulerOutput(prev_sample=prev, pred_original_sample=x0) if return_dict else (prev,)
+
+
+class UniPCMultistepScheduler:
+    """diffusers==0.24.0 UniPCMultistepScheduler (Zhao et al. 2023, "UniPC: a unified predictor-corrector framework"), restated
+    like the rest of this file (diffusers is not a dependency): a multistep predictor of order `solver_order` in the
+    data-prediction form plus a corrector that re-uses the model output of the NEXT step to raise the order by one - no
+    extra UNet call.  With the corrector off, order 2 and bh2 it is DPM-Solver++(2M).
+
+    Notation: s_j = sigmas[j] (sigma/alpha form), alpha_j = 1/sqrt(s_j^2+1), sigma_j = s_j*alpha_j, lambda_j = ln alpha_j -
+    ln sigma_j; step i is at timesteps[i] and its target is index i+1.  Both updates are linear in their operands, so the
+    schedule-dependent part is host float64 math (`scalars`, `coefficients`); the tensor update is either the torch
+    expression of `step()` (fp32) or the fused HIP kernel `aa_cfg_unipc_step_tokens`.  Dynamic thresholding, Karras sigmas,
+    the noise-prediction form (`predict_x0=False`) and `solver_p` are not implemented."""
+    order = 1
+
+    def __init__(self, num_train_timesteps=1000, beta_start=0.00085, beta_end=0.012, beta_schedule="scaled_linear",
+                 solver_order=2, prediction_type="epsilon", thresholding=False, predict_x0=True, solver_type="bh2",
+                 lower_order_final=True, disable_corrector=(), solver_p=None, use_karras_sigmas=False,
+                 timestep_spacing="linspace", steps_offset=0, **_):
+        if thresholding or use_karras_sigmas or not predict_x0 or solver_p is not None:
+            raise NotImplementedError("UniPCMultistepScheduler: thresholding / use_karras_sigmas / predict_x0=False / solver_p "
+                                      "are not implemented")
+        if solver_order not in (1, 2, 3):
+            raise ValueError(f"solver_order {solver_order!r}: 1, 2 or 3")
+        if prediction_type not in ("epsilon", "sample", "v_prediction"):
+            raise ValueError(f"prediction_type {prediction_type!r}: epsilon, sample or v_prediction")
+        if solver_type in ("midpoint", "heun", "logrho"):      # (a DPM-Solver config: diffusers registers bh2 for these)
+            solver_type = "bh2"
+        if solver_type not in ("bh1", "bh2"):
+            raise ValueError(f"solver_type {solver_type!r}: bh1 or bh2")
+        if timestep_spacing not in ("leading", "trailing", "linspace"):
+            raise ValueError(f"timestep_spacing {timestep_spacing!r}: leading, trailing or linspace")
+        self.config = SimpleNamespace(num_train_timesteps=num_train_timesteps, beta_start=beta_start, beta_end=beta_end,
+                                      beta_schedule=beta_schedule, solver_order=solver_order, prediction_type=prediction_type,
+                                      thresholding=thresholding, predict_x0=predict_x0, solver_type=solver_type,
+                                      lower_order_final=lower_order_final, disable_corrector=tuple(disable_corrector),
+                                      solver_p=solver_p, use_karras_sigmas=use_karras_sigmas,
+                                      timestep_spacing=timestep_spacing, steps_offset=steps_offset)
+        self._acp = np.cumprod(1.0 - _betas(num_train_timesteps, beta_start, beta_end, beta_schedule))
+        self.alphas_cumprod = torch.from_numpy(self._acp)
+        self.init_noise_sigma = 1.0
+        self.disable_corrector = tuple(disable_corrector)
+        self.timesteps = None
+        self.sigmas = None
+
+    @classmethod
+    def from_config(cls, config, **overrides):
+        cfg = dict(vars(config)) if isinstance(config, SimpleNamespace) else dict(config)
+        cfg.update(overrides)
+        return cls(**{k: v for k, v in cfg.items() if not k.startswith("_")})
+
+    def set_timesteps(self, num_inference_steps, device=None):
+        c, N, n = self.config, self.config.num_train_timesteps, int(num_inference_steps)
+        if c.timestep_spacing == "linspace":
+            ts = np.linspace(0, N - 1, n + 1).round()[::-1][:-1].copy().astype(np.int64)
+        elif c.timestep_spacing == "leading":
+            ts = (np.arange(0, n + 1) * (N // (n + 1))).round()[::-1][:-1].copy().astype(np.int64)
+            ts = ts + c.steps_offset
+        else:
+            ts = np.round(np.arange(N, 0, -N / n)).astype(np.int64) - 1
+        if len(set(ts.tolist())) != len(ts):
+            raise ValueError(f"{n} steps with {c.timestep_spacing!r} spacing repeat a timestep: the multistep history needs distinct ones")
+        sig = ((1 - self._acp) / self._acp) ** 0.5
+        sigmas = np.concatenate([np.interp(ts, np.arange(N), sig), [sig[0]]]).astype(np.float32)
+        self.sigmas = sigmas.astype(np.float64)
+        self.timesteps = torch.from_numpy(ts).to(device) if device is not None else torch.from_numpy(ts)
+        self._ts = [int(t) for t in ts]
+        self.num_inference_steps = n
+        self.model_outputs = [None] * 3                     # m_{i-3}, m_{i-2}, m_{i-1}
+        self.last_sample = None
+        self.lower_order_nums = 0
+        self._steps_done = 0
+        self._step_index = None
+
+    def scale_model_input(self, sample, timestep=None):
+        return sample
+
+    _alpha_sigma = staticmethod(DPMSolverMultistepScheduler._alpha_sigma)
+    add_noise = DPMSolverMultistepScheduler.add_noise
+
+    def index_for_timestep(self, timestep):
+        return self._ts.index(int(timestep))
+
+    # ---- scalar part of one step (shared by `step` and the fused kernel) -------------------------
+    @staticmethod
+    def _b(h, count, solver_type):
+        """(phi_1, B, [b_1 .. b_count]) of a step of log-SNR width h."""
+        hh = -h
+        phi1 = math.expm1(hh)
+        B = phi1 if solver_type == "bh2" else hh
+        g, f, b = phi1 / hh - 1.0, 1.0, []
+        for j in range(1, count + 1):
+            b.append(g * f / B)
+            f *= j + 1
+            g = g / hh - 1.0 / f
+        return phi1, B, b
+
+    @staticmethod
+    def _rho(r, b):
+        """Solves sum_k r_k^(j-1) rho_k = b_j, j = 1..len(r)."""
+        R = np.array([[rk ** j for rk in r] for j in range(len(r))], dtype=np.float64)
+        return [float(v) for v in np.linalg.solve(R, np.array(b[:len(r)], dtype=np.float64))]
+
+    @staticmethod
+    def scalars(sigmas, i, o_pred, o_corr, solver_type="bh2", prediction_type="epsilon"):
+        """The scalars of step i over `sigmas` (float64 sequence, sigma/alpha form) with predictor order `o_pred` and corrector
+        order `o_corr` (0: no corrector):
+          m_i     = a_x*x + a_m*e                                              (x as handed in, before the correction)
+          xhat_i  = q_l*xhat_{i-1} + q_1*m_{i-1} + q_2*m_{i-2} + q_3*m_{i-3} + q_n*m_i      (o_corr > 0; xhat_i = x otherwise)
+          x_{i+1} = p_x*xhat_i + p_0*m_i + p_1*m_{i-1} + p_2*m_{i-2}
+        Returns dict(q_l, q_1, q_2, q_3, q_n, p_x, p_0, p_1, p_2, a_x, a_m)."""
+        U = UniPCMultistepScheduler
+        al, sg, lam = {}, {}, {}
+        for j in range(max(0, i - 3), i + 2):
+            al[j], sg[j] = U._alpha_sigma(float(sigmas[j]))
+            lam[j] = math.log(al[j]) - math.log(sg[j])
+        k = dict(q_l=0.0, q_1=0.0, q_2=0.0, q_3=0.0, q_n=0.0, p_x=0.0, p_0=0.0, p_1=0.0, p_2=0.0)
+        if prediction_type == "epsilon":
+            k["a_x"], k["a_m"] = 1.0 / al[i], -sg[i] / al[i]
+        elif prediction_type == "sample":
+            k["a_x"], k["a_m"] = 0.0, 1.0
+        elif prediction_type == "v_prediction":
+            k["a_x"], k["a_m"] = al[i], -sg[i]
+        else:
+            raise ValueError(f"prediction_type {prediction_type!r}: epsilon, sample or v_prediction")
+        if o_corr:
+            o = int(o_corr)
+            if not 1 <= o <= 3 or i - o < 0:
+                raise ValueError(f"corrector order {o} at step {i}")
+            h = lam[i] - lam[i - 1]
+            phi1, B, b = U._b(h, o, solver_type)
+            r = [(lam[i - 1 - j] - lam[i - 1]) / h for j in range(1, o)] + [1.0]
+            rho = [0.5] if o == 1 else U._rho(r, b)
+            k["q_l"] = sg[i] / sg[i - 1]
+            k["q_1"] = -al[i] * phi1 + al[i] * B * sum(rho[j] / r[j] for j in range(o))
+            for j in range(o - 1):                          # D_k = (m_{i-1-k} - m_{i-1}) / r_k
+                k[f"q_{j + 2}"] = -al[i] * B * rho[j] / r[j]
+            k["q_n"] = -al[i] * B * rho[o - 1]
+        o = int(o_pred)
+        if not 1 <= o <= 3 or i - (o - 1) < 0:
+            raise ValueError(f"predictor order {o} at step {i}")
+        h = lam[i + 1] - lam[i]
+        phi1, B, b = U._b(h, max(o - 1, 1), solver_type)
+        r = [(lam[i - j] - lam[i]) / h for j in range(1, o)]
+        rho = [] if o == 1 else [0.5] if o == 2 else U._rho(r, b)
+        k["p_x"] = sg[i + 1] / sg[i]
+        k["p_0"] = -al[i + 1] * phi1 + al[i + 1] * B * sum(rho[j] / r[j] for j in range(o - 1))
+        for j in range(o - 1):                              # D_k = (m_{i-k} - m_i) / r_k
+            k[f"p_{j + 1}"] = -al[i + 1] * B * rho[j] / r[j]
+        return k
+
+    def orders(self, step_index: int, steps_done=None):
+        """(predictor order, corrector order or 0) of step `step_index` when `steps_done` steps of this run came before it
+        (default: the run began at index 0)."""
+        c, n = self.config, len(self._ts)
+        done = step_index if steps_done is None else int(steps_done)
+
+        def pred(i, d):
+            o = min(c.solver_order, n - i) if c.lower_order_final else c.solver_order
+            return min(o, d + 1)                            # (lower_order_nums = min(d, solver_order))
+        corr = pred(step_index - 1, done - 1) if done > 0 and (step_index - 1) not in self.disable_corrector else 0
+        return pred(step_index, done), corr
+
+    def coefficients(self, step_index: int, steps_done=None):
+        """`scalars` of step `step_index` with this scheduler's order bookkeeping (see `orders`), plus `corr_on`."""
+        o_pred, o_corr = self.orders(step_index, steps_done)
+        k = self.scalars(self.sigmas, step_index, o_pred, o_corr, self.config.solver_type, self.config.prediction_type)
+        k["corr_on"] = o_corr > 0
+        return k
+
+    def step(self, model_output, timestep, sample, return_dict=True):
+        """diffusers-compatible tensor update (torch ops, fp32 arithmetic)."""
+        if self._step_index is None:
+            self._step_index = self.index_for_timestep(timestep)
+        k = self.coefficients(self._step_index, self._steps_done)
+        x = sample.float()
+        m = k["a_x"] * x + k["a_m"] * model_output.float()
+        m3, m2, m1 = self.model_outputs
+        if k["corr_on"]:
+            x = k["q_l"] * self.last_sample + k["q_1"] * m1 + k["q_n"] * m
+            if k["q_2"] != 0.0:
+                x = x + k["q_2"] * m2
+            if k["q_3"] != 0.0:
+                x = x + k["q_3"] * m3
+        self.model_outputs = [m2, m1, m]
+        self.last_sample = x
+        prev = k["p_x"] * x + k["p_0"] * m
+        if k["p_1"] != 0.0:
+            prev = prev + k["p_1"] * m1
+        if k["p_2"] != 0.0:
+            prev = prev + k["p_2"] * m2
+        if self.lower_order_nums < self.config.solver_order:
+            self.lower_order_nums += 1
+        self._steps_done += 1
+        self._step_index += 1
+        prev = prev.to(sample.dtype)
+        return SchedulerOutput(prev_sample=prev, pred_original_sample=m.to(sample.dtype)) if return_dict else (prev,)
 
 
 class EulerDiscreteScheduler:

@@ -618,6 +618,43 @@ typedef struct AaDdimStepTok {
 
 int aa_cfg_ddim_step_tokens(const AaDdimStepTok* d, void* stream);
 
+/* aa_cfg_unipc_step_tokens: classifier-free guidance + one UniPCMultistepScheduler step (diffusers 0.24, data-prediction form:
+ * the corrector of the step before, then this step's predictor) reading the UNet's token matrix exactly as
+ * aa_cfg_ddim_step_tokens reads it:
+ *   e    = e_uncond + guidance * (e_text - e_uncond)
+ *   m    = a_x * x + a_m * e                                                    (x: `latents` as handed in)
+ *   xhat = q_l * last_sample + q_1 * hist1 + q_2 * hist2 + q_3 * hist3 + q_n * m   when corr_on, else xhat = x
+ *   x'   = p_x * xhat + p_0 * m + p_1 * hist1 + p_2 * hist2
+ * hist1 / hist2 / hist3 hold m of the previous / second / third previous step.  Stores x' into `latents` (and `latents_lp`),
+ * xhat into `last_sample` and m into the OLDEST history buffer handed in (hist3, else hist2, else hist1; each thread reads its
+ * element before it writes it), so the caller rotates the pointers: (hist1, hist2, hist3) <- (that buffer, hist1, hist2).
+ * The scalars are schedulers.UniPCMultistepScheduler.coefficients (float64); all arithmetic is fp32.  A history pointer
+ * may be NULL exactly when its coefficients are zero (q_1, p_1 / q_2, p_2 / q_3): a non-zero coefficient with a NULL
+ * buffer, a NULL `last_sample` and fp32 buffers that overlap are AA_E_SHAPE, and nothing is written then. */
+typedef struct AaUnipcStepTok {
+    const void* tokens;
+    void* latents;            /* fp32 [clips][channels][frames][hw], updated in place */
+    void* latents_lp;         /* storage dtype copy of the new latents, may be NULL */
+    float* last_sample;       /* fp32, latents' layout: read when corr_on, receives xhat */
+    float* hist1;             /* fp32, latents' layout, may be NULL (see above) */
+    float* hist2;
+    float* hist3;
+    float* next_t;            /* device array receiving `next_t_value` (next_t_count <= 256 entries), may be NULL */
+    int32_t next_t_count;
+    float next_t_value;
+    int32_t clips, channels, frames, hw;
+    int32_t ld;               /* row pitch of the token matrix in elements (>= channels) */
+    int32_t guidance_on;
+    float guidance;
+    float a_x, a_m;
+    int32_t corr_on;
+    float q_l, q_1, q_2, q_3, q_n;
+    float p_x, p_0, p_1, p_2;
+    int32_t dtype;
+} AaUnipcStepTok;
+
+int aa_cfg_unipc_step_tokens(const AaUnipcStepTok* d, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
