@@ -19,6 +19,7 @@
 #include "kernels/linear_rows.h"
 #include "kernels/linear_fp8.h"
 #include "kernels/glue.h"
+#include "kernels/freeu.h"
 
 namespace aa {
 
@@ -1098,6 +1099,46 @@ int aa_cfg_unipc_step_tokens(const AaUnipcStepTok* d, void* stream) {
     else if (d->dtype == AA_BF16) AA_LAUNCH((cfg_unipc_step_tok_kernel<bf16_t>), grid, block, 0, stream, *d);
     else return fail(AA_E_DTYPE, "cfg_unipc_step_tokens: unsupported dtype %d", d->dtype);
     return finish("cfg_unipc_step_tokens");
+}
+
+int aa_freeu_tokens(const AaFreeU* d, void* stream) {
+    using namespace aa;
+    if (!d || !d->hidden || !d->hidden_out || !d->skip || !d->skip_out || !d->trig) return fail(AA_E_SHAPE, "freeu_tokens: null operand");
+    if (d->images < 1 || d->h < 1 || d->w < 1 || (int64_t)d->images * d->h * d->w >= ((int64_t)1 << 31) || (int64_t)d->h * d->w >= ((int64_t)1 << 24))
+        return fail(AA_E_SHAPE, "freeu_tokens: bad geometry (images %d, h %d, w %d)", d->images, d->h, d->w);
+    if (d->c_hidden < 8 || d->c_skip < 8 || d->c_hidden % 8 || d->c_skip % 8 || d->c_hidden % 2)
+        return fail(AA_E_SHAPE, "freeu_tokens: channel counts must be multiples of 8 (c_hidden %d, c_skip %d)", d->c_hidden, d->c_skip);
+    if (d->hidden_ld < d->c_hidden || d->hidden_out_ld < d->c_hidden || d->skip_ld < d->c_skip || d->skip_out_ld < d->c_skip)
+        return fail(AA_E_SHAPE, "freeu_tokens: a row pitch is smaller than its channel count");
+    if (d->dtype != AA_F16 && d->dtype != AA_BF16) return fail(AA_E_DTYPE, "freeu_tokens: unsupported dtype %d", d->dtype);
+    if (!aligned16(d->hidden) || !aligned16(d->hidden_out) || !aligned16(d->skip) || !aligned16(d->skip_out) || !aligned16(d->trig) ||
+        d->hidden_ld % 8 || d->hidden_out_ld % 8 || d->skip_ld % 8 || d->skip_out_ld % 8)
+        return fail(AA_E_ALIGN, "freeu_tokens: pointers must be 16-byte aligned and row pitches multiples of 8 elements");
+    const int64_t rows = (int64_t)d->images * d->h * d->w;
+    struct Span { const char* p; int64_t bytes; int ld; };
+    const Span sp[5] = {{(const char*)d->hidden, ((rows - 1) * d->hidden_ld + d->c_hidden) * 2, d->hidden_ld},
+                        {(const char*)d->hidden_out, ((rows - 1) * d->hidden_out_ld + d->c_hidden) * 2, d->hidden_out_ld},
+                        {(const char*)d->skip, ((rows - 1) * d->skip_ld + d->c_skip) * 2, d->skip_ld},
+                        {(const char*)d->skip_out, ((rows - 1) * d->skip_out_ld + d->c_skip) * 2, d->skip_out_ld},
+                        {(const char*)d->trig, (int64_t)d->h * d->w * 16, 0}};
+    for (int i = 0; i < 5; ++i)
+        for (int j = i + 1; j < 5; ++j) {
+            if (!(sp[i].p < sp[j].p + sp[j].bytes && sp[j].p < sp[i].p + sp[i].bytes)) continue;
+            const bool in_place = (i == 0 && j == 1) || (i == 2 && j == 3);
+            if (in_place && sp[i].p == sp[j].p && sp[i].ld == sp[j].ld) continue;
+            return fail(AA_E_SHAPE, in_place ? "freeu_tokens: an output may be its input (same pointer and pitch) or a separate buffer, not overlap it"
+                                             : "freeu_tokens: hidden, skip, their outputs and the table must not overlap");
+        }
+    const int skip_blocks = fu_skip_blocks(*d);
+    const bool hidden_in_place = d->hidden == d->hidden_out;
+    int64_t hidden_chunks = hidden_in_place ? (d->b == 1.0f ? 0 : rows * ((d->c_hidden / 2 + 7) / 8)) : rows * (d->c_hidden / 8);
+    int64_t hidden_blocks = (hidden_chunks + 255) / 256;
+    if (hidden_blocks > 2048) hidden_blocks = 2048;
+    if (skip_blocks + hidden_blocks == 0) return AA_OK;                       // the identity in place: nothing to do
+    const dim3 grid((unsigned)(skip_blocks + hidden_blocks)), block(256);
+    if (d->dtype == AA_F16) AA_LAUNCH((freeu_tok_kernel<f16_t>), grid, block, FU_LDS_BYTES, stream, *d);
+    else AA_LAUNCH((freeu_tok_kernel<bf16_t>), grid, block, FU_LDS_BYTES, stream, *d);
+    return finish("freeu_tokens");
 }
 
 }  // extern "C"

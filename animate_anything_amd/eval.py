@@ -6,7 +6,7 @@
 Same YAML keys and dot-list overrides (`pretrained_model_path`, `validation_data.{prompt,prompt_image,mask,strength,
 num_frames,width,height,num_inference_steps,guidance_scale,fps}`, `seed`, `motion_mask`, `motion_strength`), plus
 `sampler: ddim` for the checkpoint's own DDIM scheduler or `sampler: unipc` for UniPC (the sampler for 8-12 steps) in place
-of DPM-Solver++.
+of DPM-Solver++, and `freeu: {s1: .., s2: .., b1: .., b2: ..}` for diffusers' FreeU switch.
 The third-party pieces the reference pulls in and that do not exist in this image are replaced by small
 equivalents: OmegaConf -> PyYAML + dot-list merge, `VaeImageProcessor.preprocess` -> PIL lanczos resize + [-1,1]
 scaling, torchvision `ToTensor`/`Resize(antialias=False)` -> torch bilinear interpolate, imageio -> PIL GIF writer.
@@ -208,6 +208,21 @@ def _check_sampler(sampler):
         raise ValueError(f"sampler {sampler!r}: dpm (DPM-Solver++, the default), ddim or unipc")
 
 
+FREEU_KEYS = ("s1", "s2", "b1", "b2")
+
+
+def _check_freeu(freeu):
+    """The `freeu` key: None (off) or a mapping with exactly s1, s2, b1, b2, all numbers; returns the four as floats (or None)."""
+    if freeu is None:
+        return None
+    if not isinstance(freeu, dict) or sorted(freeu) != sorted(FREEU_KEYS):
+        raise ValueError(f"freeu {freeu!r}: a mapping with exactly the keys s1, s2, b1, b2")
+    for k in FREEU_KEYS:
+        if isinstance(freeu[k], bool) or not isinstance(freeu[k], (int, float)):
+            raise ValueError(f"freeu.{k} = {freeu[k]!r}: a number")
+    return {k: float(freeu[k]) for k in FREEU_KEYS}
+
+
 def batch_eval(unet, text_encoder, vae, tokenizer, scheduler_config, validation_data, output_dir, preview,
                global_step=0, iters=6, generator=None, indices=None, seed=None, lora_path=None, lora_rank=16,
                unet_lora_modules=("UNet3DConditionModel",), guidance_group=None, sampler="dpm"):
@@ -243,7 +258,7 @@ def batch_eval(unet, text_encoder, vae, tokenizer, scheduler_config, validation_
 
 def main_eval(pretrained_model_path, validation_data, seed=None, motion_mask=None, motion_strength=None,
               output_dir="output/demo", iters=6, dtype="fp16", graph=True, lora_path=None, lora_rank=16,
-              unet_lora_modules=("UNet3DConditionModel",), guidance_parallel=False, fp8_feedforward=False, sampler="dpm", **kwargs):
+              unet_lora_modules=("UNet3DConditionModel",), guidance_parallel=False, fp8_feedforward=False, sampler="dpm", freeu=None, **kwargs):
     """train.py:825-857.  Weights are cast to half precision on the GPU ("cuda" is the HIP device on ROCm).
     The reference accepts `motion_mask` / `motion_strength` here and never forwards them to the UNet constructor
     (train.py:838: the checkpoint's config.json governs); so do we - they are passed on only when the YAML sets them.
@@ -252,6 +267,7 @@ def main_eval(pretrained_model_path, validation_data, seed=None, motion_mask=Non
     are sharded round-robin over the ranks (rank r renders samples r, r+W, ...; per-sample seed = seed + index so the
     outputs do not depend on W) and the final latents are all-gathered over RCCL (distributed.gather_clips)."""
     _check_sampler(sampler)                               # (before any model is loaded)
+    freeu = _check_freeu(freeu)
     from . import distributed as D
     rank, world, _dev = D.init()
     generator = None
@@ -267,6 +283,8 @@ def main_eval(pretrained_model_path, validation_data, seed=None, motion_mask=Non
             m.to(torch.device("cuda"), dtype=weight_dtype)
     if fp8_feedforward:                                   # config key `fp8_feedforward: true`: the opt-in e4m3 FeedForward path
         unet.enable_fp8_feedforward()
+    if freeu is not None:                                 # config key `freeu: {s1, s2, b1, b2}`: diffusers' enable_freeu
+        unet.enable_freeu(**freeu)
     if graph:
         unet.enable_graph()
     if world == 1:

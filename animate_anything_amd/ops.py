@@ -8,6 +8,7 @@ on the GPU raise, as does a missing library.
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 from dataclasses import dataclass
 from typing import Optional
@@ -16,7 +17,7 @@ import torch
 
 from . import _lib
 from ._lib import (AA_ACT_GELU, AA_ACT_NONE, AA_ACT_QUICK_GELU, AA_ACT_SILU, AA_BF16, AA_F16, AA_F32, AaAttention, AaAttnOperand,
-                   AaBlend, AaConvGemm, AaFFFused, AaLinearRows, AaLinearFp8, AaQuantRowsFp8, AaDdimStepTok, AaDpmStep, AaDpmStepTok, AaEulerStepTok, AaGroupNorm, AaPackFrames, AaPackLatents, AaSeqSelfAttn, AaUnipcStepTok)
+                   AaBlend, AaConvGemm, AaFFFused, AaLinearRows, AaLinearFp8, AaQuantRowsFp8, AaDdimStepTok, AaDpmStep, AaDpmStepTok, AaEulerStepTok, AaGroupNorm, AaPackFrames, AaPackLatents, AaSeqSelfAttn, AaUnipcStepTok, AaFreeU)
 
 _DT = {torch.float16: AA_F16, torch.bfloat16: AA_BF16, torch.float32: AA_F32}
 
@@ -1346,3 +1347,53 @@ def cfg_unipc_step_tokens(tokens, latents, latents_lp, guidance, coeffs, last_sa
     _run(lib.aa_cfg_unipc_step_tokens, C.byref(d), _stream(latents))
     live = [hbuf for hbuf in history if hbuf is not None]
     return tuple(live[-1:] + live[:-1]) + (None,) * (3 - len(live))
+
+
+# ------------------------------------------------------------------------------------- FreeU
+_FREEU_TRIG = {}
+
+
+def freeu_trig_table(h: int, w: int, device) -> torch.Tensor:
+    """fp32 [h*w, 4] = (cos ty, sin ty, cos tx, sin tx) per pixel (row-major), ty = 2 pi row / h, tx = 2 pi col / w, evaluated in
+    float64 on the host; zeros along a 1-pixel axis (aa_mi355.h AaFreeU).  Cached per (h, w, device)."""
+    key = (int(h), int(w), str(torch.device(device)))
+    t = _FREEU_TRIG.get(key)
+    if t is None:
+        ty = 2.0 * math.pi * torch.arange(h, dtype=torch.float64) / h
+        tx = 2.0 * math.pi * torch.arange(w, dtype=torch.float64) / w
+        one = lambda f, a, n: f(a) if n > 1 else torch.zeros(n, dtype=torch.float64)
+        rows = torch.stack([one(torch.cos, ty, h), one(torch.sin, ty, h)], dim=1)[:, None, :].expand(h, w, 2)
+        cols = torch.stack([one(torch.cos, tx, w), one(torch.sin, tx, w)], dim=1)[None, :, :].expand(h, w, 2)
+        t = _FREEU_TRIG[key] = torch.cat([rows, cols], dim=2).reshape(h * w, 4).to(torch.float32).contiguous().to(device)
+    return t
+
+
+def freeu(hidden: torch.Tensor, skip: torch.Tensor, images: int, h: int, w: int, b: float, s: float,
+          hidden_out: Optional[torch.Tensor] = None, skip_out: Optional[torch.Tensor] = None):
+    """FreeU on the operands of an up-block resnet, token layout [images*h*w, C] (rows may be pitched: stride(0) >= C, stride(1) == 1):
+    hidden[:, :C_hidden // 2] * b and the Fourier filter of diffusers (threshold 1, scale s) on every (image, channel) plane of
+    `skip`, one launch (aa_freeu_tokens).  An output may be its input (in place) or None (a new dense tensor).
+    Returns (hidden_out, skip_out)."""
+    lib = _lib.get()
+    rows = int(images) * int(h) * int(w)
+    for name, t in (("hidden", hidden), ("skip", skip), ("hidden_out", hidden_out), ("skip_out", skip_out)):
+        if t is None:
+            continue
+        if not t.is_cuda and not _lib.host_pointers_ok():
+            raise RuntimeError("animate_anything_amd ops run on the GPU only (tensor is on %s)" % t.device)
+        if t.dim() != 2 or (t.shape[1] > 1 and t.stride(1) != 1) or t.dtype != hidden.dtype or t.dtype not in (torch.float16, torch.bfloat16):
+            raise RuntimeError(f"freeu: {name} must be a 2-d fp16 / bf16 token matrix with contiguous rows, all of one dtype")
+        if h >= 1 and w >= 1 and images >= 1 and t.shape[0] != rows:
+            raise RuntimeError(f"freeu: {name} has {t.shape[0]} rows, images * h * w = {rows}")
+    ho = torch.empty(hidden.shape, dtype=hidden.dtype, device=hidden.device) if hidden_out is None else hidden_out
+    so = torch.empty(skip.shape, dtype=skip.dtype, device=skip.device) if skip_out is None else skip_out
+    if ho.shape != hidden.shape or so.shape != skip.shape:
+        raise RuntimeError("freeu: an output must have its input's shape")
+    d = AaFreeU()
+    d.hidden, d.hidden_out, d.skip, d.skip_out = _ptr(hidden), _ptr(ho), _ptr(skip), _ptr(so)
+    d.trig = _ptr(freeu_trig_table(max(int(h), 1), max(int(w), 1), hidden.device))      # (h or w < 1: the entry point refuses)
+    d.images, d.h, d.w, d.c_hidden, d.c_skip = int(images), int(h), int(w), hidden.shape[1], skip.shape[1]
+    d.hidden_ld, d.hidden_out_ld, d.skip_ld, d.skip_out_ld = hidden.stride(0), ho.stride(0), skip.stride(0), so.stride(0)
+    d.b, d.s, d.dtype = float(b), float(s), _DT[hidden.dtype]
+    _run(lib.aa_freeu_tokens, C.byref(d), _stream(hidden))
+    return ho, so

@@ -151,6 +151,13 @@ class LatentToVideoPipeline:
                     m.to(torch_dtype)
         return self
 
+    def enable_freeu(self, s1, s2, b1, b2):
+        """diffusers `TextToVideoSDPipeline.enable_freeu`: forwards to the UNet (UNet3DConditionModel.enable_freeu)."""
+        self.unet.enable_freeu(s1=s1, s2=s2, b1=b1, b2=b2)
+
+    def disable_freeu(self):
+        self.unet.disable_freeu()
+
     # ------------------------------------------------------------------ helpers (diffusers TextToVideoSDPipeline)
     def check_inputs(self, prompt, height, width, callback_steps, negative_prompt=None, prompt_embeds=None,
                      negative_prompt_embeds=None):

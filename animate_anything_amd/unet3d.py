@@ -88,9 +88,23 @@ class DownBlock3D(_DownStage):
 
 
 class _UpStage(_Stage):
+    resolution_idx = None                       # position in up_blocks (diffusers); FreeU acts on 0 and 1
+    s1 = s2 = b1 = b2 = None                    # FreeU scalars (UNet3DConditionModel.enable_freeu)
+
+    def _freeu(self):
+        """(b, s) of this block when FreeU is on for it - diffusers' condition: the four attributes set and non-zero, resolution_idx 0 / 1."""
+        if self.resolution_idx not in (0, 1) or not (self.s1 and self.s2 and self.b1 and self.b2):
+            return None
+        return (self.b1, self.s1) if self.resolution_idx == 0 else (self.b2, self.s2)
+
     def tokens(self, x, g, skips, temb_silu, text, text_len, upsample_size=None):
+        freeu = self._freeu()
         for i in range(len(self.resnets)):
             skip, _ = skips.pop()
+            if freeu is not None:
+                # in front of the implicit cat([x, skip]); in place: every reader of the two tensors (the down path, the mid block,
+                # the layer before) has run, and a step recomputes both
+                x, skip = ops.freeu(x, skip, g.images, g.h, g.w, freeu[0], freeu[1], hidden_out=x, skip_out=skip)
             x = self._layer(i, x, g, temb_silu, text, text_len, skip=skip)     # cat([x, skip]) is implicit
         if self.upsamplers is not None:
             x, g = self.upsamplers[0].tokens(x, g, upsample_size)
@@ -217,6 +231,7 @@ class UNet3DConditionModel(nn.Module):
             attn = dict(heads=out_c // rhd[i], head_dim=rhd[i], cross_attention_dim=cross_attention_dim) \
                 if kind.startswith("CrossAttn") else {}
             self.up_blocks.append(_UP[kind](io, temb, norm_eps, norm_num_groups, up=up, **attn))
+            self.up_blocks[-1].resolution_idx = i
 
         self.conv_norm_out = GroupNorm(norm_num_groups, ch0, eps=norm_eps)
         self.conv_act = nn.SiLU()
@@ -457,6 +472,20 @@ class UNet3DConditionModel(nn.Module):
             if isinstance(m, FeedForward):
                 m.fp8 = False
                 m._pw8 = None
+        self.invalidate_caches()
+
+    def enable_freeu(self, s1, s2, b1, b2):
+        """diffusers `enable_freeu` (FreeU, Si et al.): in the up blocks with resolution_idx 0 / 1 (the 8x8 and 16x16 levels of the v1.02
+        architecture) every resnet sees the first half of the backbone channels scaled by b1 / b2 and the skip connection with its lowest
+        Fourier modes scaled by s1 / s2 (`ops.freeu`, one launch per layer).  Off by default; the scalars are baked into captured graphs,
+        so the sessions are dropped."""
+        for blk in self.up_blocks:
+            blk.s1, blk.s2, blk.b1, blk.b2 = s1, s2, b1, b2
+        self.invalidate_caches()
+
+    def disable_freeu(self):
+        for blk in self.up_blocks:
+            blk.s1 = blk.s2 = blk.b1 = blk.b2 = None
         self.invalidate_caches()
 
     def session(self, batch, frames, h, w, text_shape, use_mask, has_motion, has_cond_emb, sample_dtype, sample_batch,

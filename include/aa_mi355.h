@@ -655,6 +655,35 @@ typedef struct AaUnipcStepTok {
 
 int aa_cfg_unipc_step_tokens(const AaUnipcStepTok* d, void* stream);
 
+/* aa_freeu_tokens: FreeU (Si et al.; diffusers 0.24 `apply_freeu` with `fourier_filter(threshold = 1)`) on the two operands of an
+ * up-block resnet in the channels-last token layout, one launch:
+ *   hidden_out[:, 0 : c_hidden / 2] = hidden[:, 0 : c_hidden / 2] * b        (the other columns copied)
+ *   skip_out = skip + (s - 1) * Re(P skip)   per (image, channel) plane of h x w pixels, P the projector on the Fourier modes
+ *              {0, h-1} x {0, w-1} - the bins rows h/2-1 : h/2+1 x columns w/2-1 : w/2+1 of the shifted spectrum that diffusers scales by s -
+ *              evaluated as (1 / hw) * sum_k (sum_pixels x * phi_k) * phi_k over 1, cos ty, sin ty, cos tx, sin tx, cos(ty + tx), sin(ty + tx)
+ *              (ty = 2 pi row / h, tx = 2 pi col / w).  fp32 sums in a fixed order (no atomics), one rounding to the storage type.
+ * `trig` is the fp32 table [h * w][4] = (cos ty, sin ty, cos tx, sin tx) of the pixels in row-major order, with zeros along an axis of
+ * one pixel.  Both tensors are [images * h * w] rows of 16-bit elements with a row pitch in elements; an output may be its input
+ * (same pointer, same pitch) or a separate buffer.  s = 1 and b = 1 reproduce the inputs bit for bit.
+ * AA_E_SHAPE, with nothing launched: a null pointer; images, h or w < 1; a channel count that is not a multiple of 8;
+ * an odd c_hidden; a pitch smaller than its channel count; an output that overlaps its input without being identical; any two
+ * different tensors (the table included) that overlap.  AA_E_ALIGN: a pointer that is not 16-byte aligned or a pitch that is not a
+ * multiple of 8 elements. */
+typedef struct AaFreeU {
+    const void* hidden;       /* [images * h * w][hidden_ld] */
+    void* hidden_out;         /* [images * h * w][hidden_out_ld] */
+    const void* skip;         /* [images * h * w][skip_ld] */
+    void* skip_out;           /* [images * h * w][skip_out_ld] */
+    const float* trig;        /* fp32 [h * w][4] */
+    int32_t images, h, w;
+    int32_t c_hidden, c_skip;
+    int32_t hidden_ld, hidden_out_ld, skip_ld, skip_out_ld;
+    float b, s;
+    int32_t dtype;            /* AA_F16 / AA_BF16 */
+} AaFreeU;
+
+int aa_freeu_tokens(const AaFreeU* d, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
