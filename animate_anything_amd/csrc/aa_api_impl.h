@@ -41,6 +41,18 @@ static int finish(const char* what) {
 
 static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
+// What the four token step entry points share: the geometry test (`ld`: row pitch of the token matrix) and the launch grid.
+template <typename D>
+static bool step_tok_geometry_ok(const D* d, int ld) {
+    return d->clips > 0 && d->channels > 0 && d->frames > 0 && d->hw > 0 && ld >= d->channels && d->next_t_count >= 0 && d->next_t_count <= 256;
+}
+
+template <typename D>
+static dim3 step_tok_grid(const D* d) {
+    const int64_t blocks = ((int64_t)d->clips * d->channels * d->frames * d->hw + 255) / 256;
+    return dim3((unsigned)(blocks > 2048 ? 2048 : blocks));
+}
+
 // Tile configurations of the LDS-DMA contraction kernel.  `rate` is the relative throughput of a tile
 // shape once the CUs are full (measured: the L2 -> LDS stream limits the narrow tiles); the chooser
 // minimises rounds(tiles / resident slots) * tile work / rate over the shapes that divide the packed width.
@@ -999,11 +1011,8 @@ int aa_pack_latents(const AaPackLatents* d, void* stream) {
 int aa_cfg_dpm_step_tokens(const AaDpmStepTok* d, void* stream) {
     using namespace aa;
     if (!d || !d->eps_tokens || !d->latents || !d->x0_prev) return fail(AA_E_SHAPE, "cfg_dpm_step_tokens: null operand");
-    if (d->clips <= 0 || d->channels <= 0 || d->frames <= 0 || d->hw <= 0 || d->eps_ld < d->channels || d->next_t_count < 0 || d->next_t_count > 256)
-        return fail(AA_E_SHAPE, "cfg_dpm_step_tokens: bad geometry");
-    int64_t blocks = ((int64_t)d->clips * d->channels * d->frames * d->hw + 255) / 256;
-    if (blocks > 2048) blocks = 2048;
-    const dim3 grid((unsigned)blocks), block(256);
+    if (!step_tok_geometry_ok(d, d->eps_ld)) return fail(AA_E_SHAPE, "cfg_dpm_step_tokens: bad geometry");
+    const dim3 grid = step_tok_grid(d), block(256);
     if (d->dtype == AA_F16) AA_LAUNCH((cfg_dpm_step_tok_kernel<f16_t>), grid, block, 0, stream, *d);
     else if (d->dtype == AA_BF16) AA_LAUNCH((cfg_dpm_step_tok_kernel<bf16_t>), grid, block, 0, stream, *d);
     else return fail(AA_E_DTYPE, "cfg_dpm_step_tokens: unsupported dtype %d", d->dtype);
@@ -1053,11 +1062,8 @@ int aa_pack_frames(const AaPackFrames* d, void* stream) {
 int aa_cfg_euler_step_tokens(const AaEulerStepTok* d, void* stream) {
     using namespace aa;
     if (!d || !d->v_tokens || !d->latents) return fail(AA_E_SHAPE, "cfg_euler_step_tokens: null operand");
-    if (d->clips <= 0 || d->channels <= 0 || d->frames <= 0 || d->hw <= 0 || d->ld < d->channels || d->next_t_count < 0 || d->next_t_count > 256)
-        return fail(AA_E_SHAPE, "cfg_euler_step_tokens: bad geometry");
-    int64_t blocks = ((int64_t)d->clips * d->channels * d->frames * d->hw + 255) / 256;
-    if (blocks > 2048) blocks = 2048;
-    const dim3 grid((unsigned)blocks), block(256);
+    if (!step_tok_geometry_ok(d, d->ld)) return fail(AA_E_SHAPE, "cfg_euler_step_tokens: bad geometry");
+    const dim3 grid = step_tok_grid(d), block(256);
     if (d->dtype == AA_F16) AA_LAUNCH((cfg_euler_step_tok_kernel<f16_t>), grid, block, 0, stream, *d);
     else if (d->dtype == AA_BF16) AA_LAUNCH((cfg_euler_step_tok_kernel<bf16_t>), grid, block, 0, stream, *d);
     else return fail(AA_E_DTYPE, "cfg_euler_step_tokens: unsupported dtype %d", d->dtype);
@@ -1067,12 +1073,9 @@ int aa_cfg_euler_step_tokens(const AaEulerStepTok* d, void* stream) {
 int aa_cfg_ddim_step_tokens(const AaDdimStepTok* d, void* stream) {
     using namespace aa;
     if (!d || !d->tokens || !d->latents) return fail(AA_E_SHAPE, "cfg_ddim_step_tokens: null operand");
-    if (d->clips <= 0 || d->channels <= 0 || d->frames <= 0 || d->hw <= 0 || d->ld < d->channels || d->next_t_count < 0 || d->next_t_count > 256)
-        return fail(AA_E_SHAPE, "cfg_ddim_step_tokens: bad geometry");
+    if (!step_tok_geometry_ok(d, d->ld)) return fail(AA_E_SHAPE, "cfg_ddim_step_tokens: bad geometry");
     if (d->c_n != 0.0f && !d->noise) return fail(AA_E_SHAPE, "cfg_ddim_step_tokens: c_n != 0 needs the noise operand");
-    int64_t blocks = ((int64_t)d->clips * d->channels * d->frames * d->hw + 255) / 256;
-    if (blocks > 2048) blocks = 2048;
-    const dim3 grid((unsigned)blocks), block(256);
+    const dim3 grid = step_tok_grid(d), block(256);
     if (d->dtype == AA_F16) AA_LAUNCH((cfg_ddim_step_tok_kernel<f16_t>), grid, block, 0, stream, *d);
     else if (d->dtype == AA_BF16) AA_LAUNCH((cfg_ddim_step_tok_kernel<bf16_t>), grid, block, 0, stream, *d);
     else return fail(AA_E_DTYPE, "cfg_ddim_step_tokens: unsupported dtype %d", d->dtype);
@@ -1082,8 +1085,7 @@ int aa_cfg_ddim_step_tokens(const AaDdimStepTok* d, void* stream) {
 int aa_cfg_unipc_step_tokens(const AaUnipcStepTok* d, void* stream) {
     using namespace aa;
     if (!d || !d->tokens || !d->latents || !d->last_sample) return fail(AA_E_SHAPE, "cfg_unipc_step_tokens: null operand");
-    if (d->clips <= 0 || d->channels <= 0 || d->frames <= 0 || d->hw <= 0 || d->ld < d->channels || d->next_t_count < 0 || d->next_t_count > 256)
-        return fail(AA_E_SHAPE, "cfg_unipc_step_tokens: bad geometry");
+    if (!step_tok_geometry_ok(d, d->ld)) return fail(AA_E_SHAPE, "cfg_unipc_step_tokens: bad geometry");
     if (((d->q_1 != 0.0f || d->p_1 != 0.0f) && !d->hist1) || ((d->q_2 != 0.0f || d->p_2 != 0.0f) && !d->hist2) || (d->q_3 != 0.0f && !d->hist3))
         return fail(AA_E_SHAPE, "cfg_unipc_step_tokens: a non-zero history coefficient needs its history buffer");
     const int64_t n = (int64_t)d->clips * d->channels * d->frames * d->hw;
@@ -1092,9 +1094,7 @@ int aa_cfg_unipc_step_tokens(const AaUnipcStepTok* d, void* stream) {
         for (int j = i + 1; j < 5; ++j)
             if (buf[i] && buf[j] && buf[i] < buf[j] + n * 4 && buf[j] < buf[i] + n * 4)
                 return fail(AA_E_SHAPE, "cfg_unipc_step_tokens: latents, last_sample and the history buffers must not overlap");
-    int64_t blocks = (n + 255) / 256;
-    if (blocks > 2048) blocks = 2048;
-    const dim3 grid((unsigned)blocks), block(256);
+    const dim3 grid = step_tok_grid(d), block(256);
     if (d->dtype == AA_F16) AA_LAUNCH((cfg_unipc_step_tok_kernel<f16_t>), grid, block, 0, stream, *d);
     else if (d->dtype == AA_BF16) AA_LAUNCH((cfg_unipc_step_tok_kernel<bf16_t>), grid, block, 0, stream, *d);
     else return fail(AA_E_DTYPE, "cfg_unipc_step_tokens: unsupported dtype %d", d->dtype);

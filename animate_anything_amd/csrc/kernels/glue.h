@@ -7,6 +7,8 @@
 //                            the next UNet input
 //  * cfg_ddim_step_tok_kernel the same for DDIMScheduler.step (the scheduler the checkpoints ship; reference app.py:64-113)
 //  * cfg_unipc_step_tok_kernel the same for UniPCMultistepScheduler.step: the corrector of the step before + this step's predictor
+// These three read the guided model output through guided_token() and differ in the solver arithmetic alone; every
+// *_step_tok_kernel hands the next timestep over through deposit_next_t().
 #pragma once
 #include "dev.h"
 #include "aa_mi355.h"
@@ -54,27 +56,38 @@ __global__ void __launch_bounds__(256) pack_latents_kernel(const AaPackLatents p
     }
 }
 
+// The guided model output of latent element i = ((clip * channels + channel) * frames + frame) * hw + pixel, read from the UNet's token
+// matrix `tok` [(2*)clips * (frames+1) * hw rows of pitch `ld`]: u, or u + guidance * (t - u) with t from the text half of the batch.
+template <typename T, typename P>
+__device__ __forceinline__ float guided_token(const T* tok, int ld, const P& p, int64_t i) {
+    const int T1 = p.frames + 1;
+    const int pix = (int)(i % p.hw);
+    int64_t r = i / p.hw;
+    const int f = (int)(r % p.frames); r /= p.frames;
+    const int c = (int)(r % p.channels);
+    const int b = (int)(r / p.channels);
+    const int64_t tok_u = ((int64_t)b * T1 + f + 1) * p.hw + pix;                       // frame 0 of the UNet output is dropped (:522)
+    const float u = (float)tok[tok_u * ld + c];
+    if (!p.guidance_on) return u;
+    const int64_t tok_t = ((int64_t)(p.clips + b) * T1 + f + 1) * p.hw + pix;           // [uncond clips | text clips] (pipeline.py:165)
+    return u + p.guidance * ((float)tok[tok_t * ld + c] - u);
+}
+
+// the next step's timestep, handed to the UNet session's `t` input (at most 256 entries: one block writes them)
+template <typename P>
+__device__ __forceinline__ void deposit_next_t(const P& p) {
+    if (p.next_t && blockIdx.x == 0 && threadIdx.x < p.next_t_count) p.next_t[threadIdx.x] = p.next_t_value;
+}
+
 template <typename T>
 __global__ void __launch_bounds__(256) cfg_dpm_step_tok_kernel(const AaDpmStepTok p) {
     const T* eps = reinterpret_cast<const T*>(p.eps_tokens);
     float* x = reinterpret_cast<float*>(p.latents);
     float* x0p = reinterpret_cast<float*>(p.x0_prev);
-    const int T1 = p.frames + 1;
     const int64_t n = (int64_t)p.clips * p.channels * p.frames * p.hw;
-    if (p.next_t && blockIdx.x == 0 && threadIdx.x < p.next_t_count) p.next_t[threadIdx.x] = p.next_t_value;
+    deposit_next_t(p);
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-        const int pix = (int)(i % p.hw);
-        int64_t r = i / p.hw;
-        const int f = (int)(r % p.frames); r /= p.frames;
-        const int c = (int)(r % p.channels);
-        const int b = (int)(r / p.channels);
-        const int64_t tok_u = ((int64_t)b * T1 + f + 1) * p.hw + pix;                   // frame 0 of the UNet output is dropped (:522)
-        const float u = (float)eps[tok_u * p.eps_ld + c];
-        float e = u;
-        if (p.guidance_on) {
-            const int64_t tok_t = ((int64_t)(p.clips + b) * T1 + f + 1) * p.hw + pix;   // [uncond clips | text clips] (pipeline.py:165)
-            e = u + p.guidance * ((float)eps[tok_t * p.eps_ld + c] - u);
-        }
+        const float e = guided_token(eps, p.eps_ld, p, i);
         const float xi = x[i];
         const float x0 = (xi - p.sigma_s * e) / p.alpha_s;
         const float nx = p.c_x * xi - p.c_d0 * x0 - p.c_d1 * (x0 - x0p[i]);
@@ -84,28 +97,16 @@ __global__ void __launch_bounds__(256) cfg_dpm_step_tok_kernel(const AaDpmStepTo
     }
 }
 
-// guidance + DDIMScheduler.step with the scalars folded by the caller (aa_mi355.h AaDdimStepTok); token addressing of
-// cfg_dpm_step_tok_kernel.  fp32 throughout; `noise` is read only when c_n != 0 (the entry point refuses a null one then).
+// guidance + DDIMScheduler.step with the scalars folded by the caller (aa_mi355.h AaDdimStepTok); the model output comes from
+// guided_token().  fp32 throughout; `noise` is read only when c_n != 0 (the entry point refuses a null one then).
 template <typename T>
 __global__ void __launch_bounds__(256) cfg_ddim_step_tok_kernel(const AaDdimStepTok p) {
     const T* tok = reinterpret_cast<const T*>(p.tokens);
     float* x = reinterpret_cast<float*>(p.latents);
-    const int T1 = p.frames + 1;
     const int64_t n = (int64_t)p.clips * p.channels * p.frames * p.hw;
-    if (p.next_t && blockIdx.x == 0 && threadIdx.x < p.next_t_count) p.next_t[threadIdx.x] = p.next_t_value;
+    deposit_next_t(p);
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-        const int pix = (int)(i % p.hw);
-        int64_t r = i / p.hw;
-        const int f = (int)(r % p.frames); r /= p.frames;
-        const int c = (int)(r % p.channels);
-        const int b = (int)(r / p.channels);
-        const int64_t tok_u = ((int64_t)b * T1 + f + 1) * p.hw + pix;                   // frame 0 of the UNet output is dropped (:522)
-        const float u = (float)tok[tok_u * p.ld + c];
-        float m = u;
-        if (p.guidance_on) {
-            const int64_t tok_t = ((int64_t)(p.clips + b) * T1 + f + 1) * p.hw + pix;   // [uncond clips | text clips] (pipeline.py:165)
-            m = u + p.guidance * ((float)tok[tok_t * p.ld + c] - u);
-        }
+        const float m = guided_token(tok, p.ld, p, i);
         const float xi = x[i];
         float x0 = p.a_x * xi + p.a_m * m;
         if (p.clip_on) x0 = fminf(fmaxf(x0, -p.clip), p.clip);
@@ -118,7 +119,7 @@ __global__ void __launch_bounds__(256) cfg_ddim_step_tok_kernel(const AaDdimStep
 }
 
 // guidance + one UniPC step (corrector of the step before, then the predictor) with the scalars folded by the caller
-// (aa_mi355.h AaUnipcStepTok); token addressing of cfg_ddim_step_tok_kernel.  fp32 throughout.  Every buffer is read and written
+// (aa_mi355.h AaUnipcStepTok); the model output comes from guided_token().  fp32 throughout.  Every buffer is read and written
 // at element i by the thread that owns i alone, and m goes into the oldest history buffer after that thread has read it: the
 // entry point refuses overlapping buffers and a null one whose coefficient is not zero.
 template <typename T>
@@ -126,22 +127,10 @@ __global__ void __launch_bounds__(256) cfg_unipc_step_tok_kernel(const AaUnipcSt
     const T* tok = reinterpret_cast<const T*>(p.tokens);
     float* x = reinterpret_cast<float*>(p.latents);
     float* m_out = p.hist3 ? p.hist3 : p.hist2 ? p.hist2 : p.hist1;
-    const int T1 = p.frames + 1;
     const int64_t n = (int64_t)p.clips * p.channels * p.frames * p.hw;
-    if (p.next_t && blockIdx.x == 0 && threadIdx.x < p.next_t_count) p.next_t[threadIdx.x] = p.next_t_value;
+    deposit_next_t(p);
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-        const int pix = (int)(i % p.hw);
-        int64_t r = i / p.hw;
-        const int f = (int)(r % p.frames); r /= p.frames;
-        const int c = (int)(r % p.channels);
-        const int b = (int)(r / p.channels);
-        const int64_t tok_u = ((int64_t)b * T1 + f + 1) * p.hw + pix;                   // frame 0 of the UNet output is dropped (:522)
-        const float u = (float)tok[tok_u * p.ld + c];
-        float e = u;
-        if (p.guidance_on) {
-            const int64_t tok_t = ((int64_t)(p.clips + b) * T1 + f + 1) * p.hw + pix;   // [uncond clips | text clips] (pipeline.py:165)
-            e = u + p.guidance * ((float)tok[tok_t * p.ld + c] - u);
-        }
+        const float e = guided_token(tok, p.ld, p, i);
         const float xi = x[i];
         const float m = p.a_x * xi + p.a_m * e;
         const float m1 = (p.q_1 != 0.0f || p.p_1 != 0.0f) ? p.hist1[i] : 0.0f;
@@ -251,7 +240,7 @@ __global__ void __launch_bounds__(256) cfg_euler_step_tok_kernel(const AaEulerSt
     const T* vt = reinterpret_cast<const T*>(p.v_tokens);
     float* x = reinterpret_cast<float*>(p.latents);
     const int64_t n = (int64_t)p.clips * p.frames * p.channels * p.hw;
-    if (p.next_t && blockIdx.x == 0 && threadIdx.x < p.next_t_count) p.next_t[threadIdx.x] = p.next_t_value;
+    deposit_next_t(p);
     if (p.next_scale && blockIdx.x == 0 && threadIdx.x == 0) *p.next_scale = p.next_scale_value;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
         const int pix = (int)(i % p.hw);

@@ -1195,21 +1195,45 @@ def pack_latents(sample: torch.Tensor, cond: torch.Tensor, mask: Optional[torch.
     return y
 
 
-def cfg_dpm_step_tokens(eps_tokens, latents, x0_prev, latents_lp, guidance, coeffs, next_t=None, next_t_value=0.0):
-    """Fused CFG + DPM-Solver++ update reading the UNet's token-layout output [(2*)clips*(T+1)*hw, eps_ld]."""
+def _step_tok_common(name, d, tokens, latents, latents_lp, guidance, next_t, next_t_value, state=()):
+    """What the three UNet3D token steps share: the operand checks and the descriptor fields for the token matrix, the fp32
+    latents, their 16-bit copy, the next-timestep deposit, the geometry and the guidance.  `state`: (what, tensor or None) pairs of
+    the sampler's further fp32 operands in the latents' shape.  Returns (library, stream)."""
     lib = _lib.get()
-    _check(eps_tokens, latents, x0_prev, latents_lp, next_t)
+    _check(tokens, latents, latents_lp, next_t, *(t for _, t in state))
+    if latents.dtype != torch.float32 or latents.dim() != 5:
+        raise RuntimeError(f"{name}: latents must be fp32 [clips, C, T, h, w]")
+    for what, t in state:
+        if t is not None and (t.shape != latents.shape or t.dtype != torch.float32):
+            raise RuntimeError(f"{name}: {what} must be fp32 in the latents' shape")
+    if latents_lp is not None and (latents_lp.shape != latents.shape or latents_lp.dtype != tokens.dtype):
+        raise RuntimeError(f"{name}: latents_lp must have the latents' shape and the tokens' dtype")
+    if next_t is not None and next_t.dtype != torch.float32:
+        raise RuntimeError(f"{name}: next_t must be fp32")
     clips, c, frames, h, w = latents.shape
-    d = AaDpmStepTok()
-    d.eps_tokens, d.latents, d.x0_prev, d.latents_lp = _ptr(eps_tokens), _ptr(latents), _ptr(x0_prev), _ptr(latents_lp)
+    rows = (2 if guidance is not None else 1) * clips * (frames + 1) * h * w
+    if tokens.dim() != 2 or tokens.shape[0] < rows or tokens.shape[1] < c:
+        raise RuntimeError(f"{name}: tokens {tuple(tokens.shape)} do not hold {rows} rows of {c} channels")
+    if isinstance(d, AaDpmStepTok):
+        d.eps_tokens, d.eps_ld = _ptr(tokens), tokens.stride(0)
+    else:
+        d.tokens, d.ld = _ptr(tokens), tokens.stride(0)
+    d.latents, d.latents_lp = _ptr(latents), _ptr(latents_lp)
     d.next_t, d.next_t_count, d.next_t_value = _ptr(next_t), 0 if next_t is None else next_t.numel(), float(next_t_value)
     d.clips, d.channels, d.frames, d.hw = clips, c, frames, h * w
-    d.eps_ld = eps_tokens.stride(0)
     d.guidance_on, d.guidance = int(guidance is not None), float(guidance or 0.0)
+    d.dtype = _DT[tokens.dtype]
+    return lib, _stream(latents)
+
+
+def cfg_dpm_step_tokens(eps_tokens, latents, x0_prev, latents_lp, guidance, coeffs, next_t=None, next_t_value=0.0):
+    """Fused CFG + DPM-Solver++ update reading the UNet's token-layout output [(2*)clips*(T+1)*hw, eps_ld]."""
+    d = AaDpmStepTok()
+    lib, stream = _step_tok_common("cfg_dpm_step_tokens", d, eps_tokens, latents, latents_lp, guidance, next_t, next_t_value,
+                                   (("x0_prev", x0_prev),))
+    d.x0_prev = _ptr(x0_prev)
     d.sigma_s, d.alpha_s, d.c_x, d.c_d0, d.c_d1 = (coeffs[k] for k in ("sigma_s", "alpha_s", "c_x", "c_d0", "c_d1"))
-    d.dtype = _DT[eps_tokens.dtype]
-    assert latents.dtype == torch.float32 and x0_prev.dtype == torch.float32
-    _run(lib.aa_cfg_dpm_step_tokens, C.byref(d), _stream(latents))
+    _run(lib.aa_cfg_dpm_step_tokens, C.byref(d), stream)
 
 
 # ------------------------------------------------------------------------------------- Stable-Video-Diffusion glue
@@ -1281,30 +1305,14 @@ def cfg_ddim_step_tokens(tokens, latents, latents_lp, guidance, coeffs, noise=No
     """Fused CFG + DDIM update reading the UNet's token-layout output [(2*)clips*(T+1)*hw, ld]; latents fp32 [clips, C, T, h, w]
     updated in place.  `coeffs` is schedulers.DDIMScheduler.coefficients(); `noise` (fp32, the latents' shape) is needed when
     coeffs["c_n"] != 0 (eta > 0)."""
-    lib = _lib.get()
-    _check(tokens, latents, latents_lp, noise, next_t)
-    if latents.dtype != torch.float32 or latents.dim() != 5:
-        raise RuntimeError("cfg_ddim_step_tokens: latents must be fp32 [clips, C, T, h, w]")
-    if noise is not None and (noise.shape != latents.shape or noise.dtype != torch.float32):
-        raise RuntimeError("cfg_ddim_step_tokens: noise must be fp32 in the latents' shape")
-    if latents_lp is not None and (latents_lp.shape != latents.shape or latents_lp.dtype != tokens.dtype):
-        raise RuntimeError("cfg_ddim_step_tokens: latents_lp must have the latents' shape and the tokens' dtype")
-    if next_t is not None and next_t.dtype != torch.float32:
-        raise RuntimeError("cfg_ddim_step_tokens: next_t must be fp32")
-    clips, c, frames, h, w = latents.shape
-    rows = (2 if guidance is not None else 1) * clips * (frames + 1) * h * w
-    if tokens.dim() != 2 or tokens.shape[0] < rows or tokens.shape[1] < c:
-        raise RuntimeError(f"cfg_ddim_step_tokens: tokens {tuple(tokens.shape)} do not hold {rows} rows of {c} channels")
     d = AaDdimStepTok()
-    d.tokens, d.latents, d.latents_lp, d.noise = _ptr(tokens), _ptr(latents), _ptr(latents_lp), _ptr(noise)
-    d.next_t, d.next_t_count, d.next_t_value = _ptr(next_t), 0 if next_t is None else next_t.numel(), float(next_t_value)
-    d.clips, d.channels, d.frames, d.hw, d.ld = clips, c, frames, h * w, tokens.stride(0)
-    d.guidance_on, d.guidance = int(guidance is not None), float(guidance or 0.0)
+    lib, stream = _step_tok_common("cfg_ddim_step_tokens", d, tokens, latents, latents_lp, guidance, next_t, next_t_value,
+                                   (("noise", noise),))
+    d.noise = _ptr(noise)
     d.a_x, d.a_m, d.e_x, d.e_m, d.q_x, d.q_0 = (coeffs[k] for k in ("a_x", "a_m", "e_x", "e_m", "q_x", "q_0"))
     d.c_0, d.c_e, d.c_n = (coeffs[k] for k in ("c_0", "c_e", "c_n"))
     d.clip_on, d.clip, d.eps_from_x0 = int(coeffs["clip"] is not None), float(coeffs["clip"] or 0.0), int(coeffs["eps_from_x0"])
-    d.dtype = _DT[tokens.dtype]
-    _run(lib.aa_cfg_ddim_step_tokens, C.byref(d), _stream(latents))
+    _run(lib.aa_cfg_ddim_step_tokens, C.byref(d), stream)
 
 
 def cfg_unipc_step_tokens(tokens, latents, latents_lp, guidance, coeffs, last_sample, history, next_t=None, next_t_value=0.0):
@@ -1314,37 +1322,20 @@ def cfg_unipc_step_tokens(tokens, latents, latents_lp, guidance, coeffs, last_sa
     `history` = (m of the previous step, of the second previous, of the third previous), fp32 in the latents' shape, an entry
     may be None where its coefficients are zero.  The kernel writes this step's m into the last entry that is not None;
     returns the history rotated for the next step."""
-    lib = _lib.get()
     history = tuple(history)
     if len(history) != 3:
         raise RuntimeError("cfg_unipc_step_tokens: history must hold three entries (tensors or None)")
-    _check(tokens, latents, latents_lp, last_sample, *history, next_t)
-    if latents.dtype != torch.float32 or latents.dim() != 5:
-        raise RuntimeError("cfg_unipc_step_tokens: latents must be fp32 [clips, C, T, h, w]")
-    if last_sample is None or last_sample.shape != latents.shape or last_sample.dtype != torch.float32:
+    if last_sample is None:
         raise RuntimeError("cfg_unipc_step_tokens: last_sample must be fp32 in the latents' shape")
-    for hbuf in history:
-        if hbuf is not None and (hbuf.shape != latents.shape or hbuf.dtype != torch.float32):
-            raise RuntimeError("cfg_unipc_step_tokens: history buffers must be fp32 in the latents' shape")
-    if latents_lp is not None and (latents_lp.shape != latents.shape or latents_lp.dtype != tokens.dtype):
-        raise RuntimeError("cfg_unipc_step_tokens: latents_lp must have the latents' shape and the tokens' dtype")
-    if next_t is not None and next_t.dtype != torch.float32:
-        raise RuntimeError("cfg_unipc_step_tokens: next_t must be fp32")
-    clips, c, frames, h, w = latents.shape
-    rows = (2 if guidance is not None else 1) * clips * (frames + 1) * h * w
-    if tokens.dim() != 2 or tokens.shape[0] < rows or tokens.shape[1] < c:
-        raise RuntimeError(f"cfg_unipc_step_tokens: tokens {tuple(tokens.shape)} do not hold {rows} rows of {c} channels")
     d = AaUnipcStepTok()
-    d.tokens, d.latents, d.latents_lp, d.last_sample = _ptr(tokens), _ptr(latents), _ptr(latents_lp), _ptr(last_sample)
+    lib, stream = _step_tok_common("cfg_unipc_step_tokens", d, tokens, latents, latents_lp, guidance, next_t, next_t_value,
+                                   (("last_sample", last_sample),) + tuple(("history buffers", hbuf) for hbuf in history))
+    d.last_sample = _ptr(last_sample)
     d.hist1, d.hist2, d.hist3 = (_ptr(hbuf) for hbuf in history)
-    d.next_t, d.next_t_count, d.next_t_value = _ptr(next_t), 0 if next_t is None else next_t.numel(), float(next_t_value)
-    d.clips, d.channels, d.frames, d.hw, d.ld = clips, c, frames, h * w, tokens.stride(0)
-    d.guidance_on, d.guidance = int(guidance is not None), float(guidance or 0.0)
     d.a_x, d.a_m, d.corr_on = coeffs["a_x"], coeffs["a_m"], int(bool(coeffs["corr_on"]))
     d.q_l, d.q_1, d.q_2, d.q_3, d.q_n = (coeffs[k] for k in ("q_l", "q_1", "q_2", "q_3", "q_n"))
     d.p_x, d.p_0, d.p_1, d.p_2 = (coeffs[k] for k in ("p_x", "p_0", "p_1", "p_2"))
-    d.dtype = _DT[tokens.dtype]
-    _run(lib.aa_cfg_unipc_step_tokens, C.byref(d), _stream(latents))
+    _run(lib.aa_cfg_unipc_step_tokens, C.byref(d), stream)
     live = [hbuf for hbuf in history if hbuf is not None]
     return tuple(live[-1:] + live[:-1]) + (None,) * (3 - len(live))
 

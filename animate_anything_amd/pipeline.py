@@ -4,9 +4,9 @@ helpers of /root/reference/utils/common.py:12-48,296-300.
 
 Same keyword arguments, same return convention (`(frames, latents)` when `return_dict=False`,
 pipeline.py:211-212).  Per denoising step the device work is: one UNet3D forward on the CFG-doubled
-batch (hipGraph replay when enabled) and one fused guidance + DPM-Solver++ update kernel
-(`aa_cfg_dpm_step`) -- the reference's cat / chunk / permute / scheduler.step chain
-(pipeline.py:165-192) collapses into those two.
+batch (hipGraph replay when enabled) and one fused guidance + solver update kernel
+(`aa_cfg_dpm_step_tokens`, `aa_cfg_ddim_step_tokens` or `aa_cfg_unipc_step_tokens`) -- the reference's
+cat / chunk / permute / scheduler.step chain (pipeline.py:165-192) collapses into those two.
 """
 from __future__ import annotations
 
@@ -218,117 +218,75 @@ class LatentToVideoPipeline:
                                          callback, callback_steps, eta, generator)
         dev = latents.device
         b0, _, frames, h, w = latents.shape
-        if cfg and self.guidance_group is not None:
-            return self._denoise_guidance_parallel(latents, prompt_embeds, condition_latent, mask, motion, timesteps,
-                                                   guidance_scale, callback, callback_steps, eta, generator)
-        b = 2 * b0 if cfg else b0
         use_mask = bool(unet.motion_mask and mask is not None)
         has_motion = bool(unet.motion_strength and motion is not None)
-        # under guidance both halves of the UNet batch see the same latents / condition frame / mask / timestep / motion and
-        # differ only in the text: the UNet computes the text-independent prefix once (UNet3DConditionModel._core cfg_dup)
-        shared = cfg and self.cfg_shared_prefix and b0 % condition_latent.shape[0] == 0 and (not use_mask or b0 % mask.shape[0] == 0)
-        sess = unet.session(b, frames, h, w, tuple(prompt_embeds.shape[1:]), use_mask, has_motion, False, torch.float32, b0,
+        pair = self.guidance_group if cfg else None
+        if pair is not None:
+            # Latency mode: this rank runs ONE half of the guidance batch (role 0: unconditional context = first half of `prompt_embeds`,
+            # role 1: the text half), the pair exchanges the UNet outputs with one all-gather per step (RCCL over xGMI) and both ranks
+            # apply the identical guidance + solver update to their copy of the latents.  Same arithmetic per element (the two halves of
+            # a guidance batch never interact inside the UNet); eta > 0: both ranks must hold generators in the same state.
+            from . import distributed as D
+            role, group = pair
+            b, text, shared = b0, prompt_embeds[role * b0:(role + 1) * b0], False
+        else:
+            # under guidance both halves of the UNet batch see the same latents / condition frame / mask / timestep / motion and
+            # differ only in the text: the UNet computes the text-independent prefix once (UNet3DConditionModel._core cfg_dup)
+            b, text = 2 * b0 if cfg else b0, prompt_embeds
+            shared = cfg and self.cfg_shared_prefix and b0 % condition_latent.shape[0] == 0 and (not use_mask or b0 % mask.shape[0] == 0)
+        sess = unet.session(b, frames, h, w, tuple(text.shape[1:]), use_mask, has_motion, False, torch.float32, b0,
                             condition_latent.shape[0], mask.shape[0] if use_mask else 0, dev, cfg_dup=shared)
+        tokens = sess.run                                       # [b*(T+1)*h*w, 8], columns [0, out_channels) valid (row pitch = stride(0))
+        if pair is not None:
+            # (the token matrix is padded to 8 columns: only conv_out's channels travel - 0.28 MB per rank at 16x64x64)
+            tokens = lambda: D.all_gather_cat(sess.run()[:, :unet.conv_out.out_channels], group)   # [uncond clips | text clips], the layout the solver kernel reads
         mot = None
         if has_motion:
             mot = torch.as_tensor(motion, device=dev).to(torch.float32).reshape(-1).expand(b).contiguous()
         ts = [int(t) for t in timesteps]
-        sess.load(sample=latents, cond=condition_latent, mask=mask if use_mask else None, text=prompt_embeds, motion=mot,
+        sess.load(sample=latents, cond=condition_latent, mask=mask if use_mask else None, text=text, motion=mot,
                   t=torch.full((b,), float(ts[0]) if ts else 0.0, dtype=torch.float32, device=dev))
         x = sess.inputs["sample"]                               # fp32 [b0,C,T,h,w]: updated in place by the solver kernel
-        if isinstance(sched, DDIMScheduler):
-            for i, t in enumerate(ts):
-                self._ddim_step(sess.run(), x, guidance_scale if cfg else None, t, eta, generator, sess.inputs["t"],
-                                float(ts[i + 1]) if i + 1 < len(ts) else float(t))
-                if callback is not None and i % callback_steps == 0:
-                    callback(i, t, x)
-            return x.clone()
-        if isinstance(sched, UniPCMultistepScheduler):
-            state = self._unipc_state(x)
-            for i, t in enumerate(ts):
-                self._unipc_step(sess.run(), x, guidance_scale if cfg else None, t, i, state, sess.inputs["t"],
-                                 float(ts[i + 1]) if i + 1 < len(ts) else float(t))
-                if callback is not None and i % callback_steps == 0:
-                    callback(i, t, x)
-            return x.clone()
-        x0_prev = torch.zeros_like(x)
+        step = self._solver_step(x, eta, generator)
         for i, t in enumerate(ts):
-            eps = sess.run()                                    # tokens [b*(T+1)*h*w, 8], columns [0, out_channels) valid (row pitch = stride(0))
-            k = sched.coefficients(sched.index_for_timestep(t), i > 0)
-            ops.cfg_dpm_step_tokens(eps, x, x0_prev, None, guidance_scale if cfg else None, k,
-                                    next_t=sess.inputs["t"], next_t_value=float(ts[i + 1]) if i + 1 < len(ts) else float(t))
+            step(tokens(), guidance_scale if cfg else None, t, i, sess.inputs["t"], float(ts[i + 1]) if i + 1 < len(ts) else float(t))
             if callback is not None and i % callback_steps == 0:
                 callback(i, t, x)
         return x.clone()
 
-    def _ddim_step(self, tokens, x, guidance, t, eta, generator, next_t, next_t_value):
-        """One fused guidance + DDIM update of the fp32 latents `x` from the UNet's token-layout output.  eta > 0 draws the
-        step's variance noise first (one torch.randn + the relayout into the latents' order; eta = 0 launches nothing else)."""
+    def _solver_step(self, x, eta, generator):
+        """The scheduler's part of the fused loop: returns step(tokens, guidance, t, i, next_t, next_t_value), one fused guidance +
+        solver update of the fp32 latents `x` from the UNet's token-layout output (`i` counts the steps of this run before it).  The
+        closure owns the solver state: the previous x0 for DPM-Solver++, the four buffers of `_unipc_state` (history rotated per step)
+        for UniPC, none for DDIM, where eta > 0 draws the step's variance noise first (one torch.randn + the relayout into the
+        latents' order; eta = 0 launches nothing else)."""
         sched = self.scheduler
-        k = sched.coefficients(sched.index_for_timestep(t), eta)
-        noise = _latent_layout(_variance_noise(x, generator), x) if eta > 0 else None
-        ops.cfg_ddim_step_tokens(tokens, x, None, guidance, k, noise=noise if k["c_n"] != 0.0 else None,
-                                 next_t=next_t, next_t_value=next_t_value)
+        if isinstance(sched, DDIMScheduler):
+            def step(tokens, guidance, t, i, next_t, next_t_value):
+                k = sched.coefficients(sched.index_for_timestep(t), eta)
+                noise = _latent_layout(_variance_noise(x, generator), x) if eta > 0 else None
+                ops.cfg_ddim_step_tokens(tokens, x, None, guidance, k, noise=noise if k["c_n"] != 0.0 else None,
+                                         next_t=next_t, next_t_value=next_t_value)
+        elif isinstance(sched, UniPCMultistepScheduler):
+            state = self._unipc_state(x)
+
+            def step(tokens, guidance, t, i, next_t, next_t_value):
+                k = sched.coefficients(sched.index_for_timestep(t), i)
+                state[1:] = ops.cfg_unipc_step_tokens(tokens, x, None, guidance, k, state[0], state[1:],
+                                                      next_t=next_t, next_t_value=next_t_value)
+        else:
+            x0_prev = torch.zeros_like(x)
+
+            def step(tokens, guidance, t, i, next_t, next_t_value):
+                k = sched.coefficients(sched.index_for_timestep(t), i > 0)
+                ops.cfg_dpm_step_tokens(tokens, x, x0_prev, None, guidance, k, next_t=next_t, next_t_value=next_t_value)
+        return step
 
     @staticmethod
     def _unipc_state(x):
         """The four fp32 buffers a UniPC run keeps next to the latents: [corrected sample, m of the previous step, of the second
         previous, of the third previous] (zeroed: a coefficient of zero must not meet a NaN)."""
         return [torch.zeros_like(x) for _ in range(4)]
-
-    def _unipc_step(self, tokens, x, guidance, t, steps_done, state, next_t, next_t_value):
-        """One fused guidance + UniPC step (corrector of the step before + predictor) of the fp32 latents `x` from the UNet's
-        token-layout output; `steps_done` counts the steps of this run before it.  Rotates the history in `state`."""
-        sched = self.scheduler
-        k = sched.coefficients(sched.index_for_timestep(t), steps_done)
-        state[1:] = ops.cfg_unipc_step_tokens(tokens, x, None, guidance, k, state[0], state[1:],
-                                              next_t=next_t, next_t_value=next_t_value)
-
-    def _denoise_guidance_parallel(self, latents, prompt_embeds, condition_latent, mask, motion, timesteps, guidance_scale,
-                                   callback=None, callback_steps=1, eta=0.0, generator=None):
-        """Latency mode: this rank runs ONE half of the guidance batch (role 0: unconditional context = first half of
-        `prompt_embeds`, role 1: the text half), the pair exchanges the UNet outputs with one all-gather per step (RCCL over
-        xGMI; 0.56 MB per rank at 16x64x64) and both ranks apply the identical guidance + solver update to their copy of the
-        latents.  Same arithmetic per element as `denoise` (the two halves of a guidance batch never interact inside the UNet)."""
-        from . import distributed as D
-        role, group = self.guidance_group
-        sched, unet, dev = self.scheduler, self.unet, latents.device
-        b0, _, frames, h, w = latents.shape
-        use_mask = bool(unet.motion_mask and mask is not None)
-        has_motion = bool(unet.motion_strength and motion is not None)
-        text = prompt_embeds[role * b0:(role + 1) * b0]
-        sess = unet.session(b0, frames, h, w, tuple(text.shape[1:]), use_mask, has_motion, False, torch.float32, b0,
-                            condition_latent.shape[0], mask.shape[0] if use_mask else 0, dev, cfg_dup=False)
-        mot = None
-        if has_motion:
-            mot = torch.as_tensor(motion, device=dev).to(torch.float32).reshape(-1).expand(b0).contiguous()
-        ts = [int(t) for t in timesteps]
-        sess.load(sample=latents, cond=condition_latent, mask=mask if use_mask else None, text=text, motion=mot,
-                  t=torch.full((b0,), float(ts[0]) if ts else 0.0, dtype=torch.float32, device=dev))
-        x = sess.inputs["sample"]
-        x0_prev = torch.zeros_like(x)
-        state = self._unipc_state(x) if isinstance(sched, UniPCMultistepScheduler) else None
-        for i, t in enumerate(ts):
-            # (the UNet's token matrix is padded to 8 columns: only conv_out's channels travel - 0.28 MB per rank at 16x64x64)
-            eps = D.all_gather_cat(sess.run()[:, :unet.conv_out.out_channels], group)          # [uncond clips | text clips], the layout the solver kernel reads
-            if isinstance(sched, DDIMScheduler):                 # (eta > 0: both ranks must hold generators in the same state)
-                self._ddim_step(eps, x, guidance_scale, t, eta, generator, sess.inputs["t"],
-                                float(ts[i + 1]) if i + 1 < len(ts) else float(t))
-                if callback is not None and i % callback_steps == 0:
-                    callback(i, t, x)
-                continue
-            if state is not None:
-                self._unipc_step(eps, x, guidance_scale, t, i, state, sess.inputs["t"],
-                                 float(ts[i + 1]) if i + 1 < len(ts) else float(t))
-                if callback is not None and i % callback_steps == 0:
-                    callback(i, t, x)
-                continue
-            k = sched.coefficients(sched.index_for_timestep(t), i > 0)
-            ops.cfg_dpm_step_tokens(eps, x, x0_prev, None, guidance_scale, k,
-                                    next_t=sess.inputs["t"], next_t_value=float(ts[i + 1]) if i + 1 < len(ts) else float(t))
-            if callback is not None and i % callback_steps == 0:
-                callback(i, t, x)
-        return x.clone()
 
     def _denoise_generic(self, latents, prompt_embeds, condition_latent, mask, motion, timesteps, guidance_scale,
                          callback=None, callback_steps=1, eta=0.0, generator=None):

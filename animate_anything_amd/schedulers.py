@@ -36,25 +36,54 @@ def _betas(num_train_timesteps, beta_start, beta_end, beta_schedule):
     raise NotImplementedError(f"{beta_schedule} is not implemented")
 
 
+def _alphas_cumprod(num_train_timesteps, beta_start, beta_end, beta_schedule):
+    return np.cumprod(1.0 - _betas(num_train_timesteps, beta_start, beta_end, beta_schedule))
+
+
+class _Scheduler:
+    """What the samplers below share: `from_config`, the identity `scale_model_input`, the timestep lookup over `self._ts` and the
+    sigma schedule of the multistep solvers."""
+    order = 1
+
+    @classmethod
+    def from_config(cls, config, **overrides):
+        cfg = dict(vars(config)) if isinstance(config, SimpleNamespace) else dict(config)
+        cfg.update(overrides)
+        return cls(**{k: v for k, v in cfg.items() if not k.startswith("_")})
+
+    def scale_model_input(self, sample, timestep=None):
+        return sample
+
+    def index_for_timestep(self, timestep):
+        return self._ts.index(int(timestep))
+
+    def _set_sigma_schedule(self, ts, device):
+        """The tail of `set_timesteps` of DPM-Solver++ and UniPC: `sigmas` (sigma/alpha form, rounded to float32 like diffusers)
+        at the timesteps `ts` plus the final one, `timesteps` and the lookup list from `self._acp`."""
+        sig = ((1 - self._acp) / self._acp) ** 0.5
+        sigmas = np.concatenate([np.interp(ts, np.arange(len(sig)), sig), [sig[0]]]).astype(np.float32)
+        self.sigmas = sigmas.astype(np.float64)
+        self.timesteps = torch.from_numpy(ts).to(device) if device is not None else torch.from_numpy(ts)
+        self._ts = [int(t) for t in ts]
+
+
 class DDPMScheduler:
     """Only what the eval path needs: the forward-noising `add_noise`."""
 
     def __init__(self, num_train_timesteps=1000, beta_start=0.00085, beta_end=0.012, beta_schedule="scaled_linear", **_):
         self.config = SimpleNamespace(num_train_timesteps=num_train_timesteps, beta_start=beta_start,
                                       beta_end=beta_end, beta_schedule=beta_schedule)
-        self.alphas_cumprod = torch.from_numpy(np.cumprod(1.0 - _betas(num_train_timesteps, beta_start, beta_end, beta_schedule)))
+        self.alphas_cumprod = torch.from_numpy(_alphas_cumprod(num_train_timesteps, beta_start, beta_end, beta_schedule))
 
     def add_noise(self, original_samples, noise, timesteps):
-        acp = self.alphas_cumprod.to(original_samples.device)[timesteps.to(original_samples.device).long()]
+        acp = self.alphas_cumprod.to(original_samples.device)[torch.as_tensor(timesteps).to(original_samples.device).long()]
         shape = (-1,) + (1,) * (original_samples.dim() - 1)
         a = acp.sqrt().reshape(shape).to(original_samples.dtype)
         s = (1 - acp).sqrt().reshape(shape).to(original_samples.dtype)
         return a * original_samples + s * noise
 
 
-class DPMSolverMultistepScheduler:
-    order = 1
-
+class DPMSolverMultistepScheduler(_Scheduler):
     def __init__(self, num_train_timesteps=1000, beta_start=0.00085, beta_end=0.012, beta_schedule="scaled_linear",
                  solver_order=2, prediction_type="epsilon", algorithm_type="dpmsolver++", solver_type="midpoint",
                  lower_order_final=True, timestep_spacing="leading", steps_offset=1, **_):
@@ -65,17 +94,11 @@ class DPMSolverMultistepScheduler:
                                       prediction_type=prediction_type, algorithm_type=algorithm_type,
                                       solver_type=solver_type, lower_order_final=lower_order_final,
                                       timestep_spacing=timestep_spacing, steps_offset=steps_offset)
-        self._acp = np.cumprod(1.0 - _betas(num_train_timesteps, beta_start, beta_end, beta_schedule))
+        self._acp = _alphas_cumprod(num_train_timesteps, beta_start, beta_end, beta_schedule)
         self.alphas_cumprod = torch.from_numpy(self._acp)
         self.init_noise_sigma = 1.0
         self.timesteps = None
         self.sigmas = None
-
-    @classmethod
-    def from_config(cls, config, **overrides):
-        cfg = dict(vars(config)) if isinstance(config, SimpleNamespace) else dict(config)
-        cfg.update(overrides)
-        return cls(**{k: v for k, v in cfg.items() if not k.startswith("_")})
 
     def set_timesteps(self, num_inference_steps, device=None):
         c, N = self.config, self.config.num_train_timesteps
@@ -86,18 +109,11 @@ class DPMSolverMultistepScheduler:
             ts = ts + c.steps_offset
         else:
             raise NotImplementedError(c.timestep_spacing)
-        sig = ((1 - self._acp) / self._acp) ** 0.5
-        sigmas = np.concatenate([np.interp(ts, np.arange(N), sig), [sig[0]]]).astype(np.float32)
-        self.sigmas = sigmas.astype(np.float64)
-        self.timesteps = torch.from_numpy(ts).to(device) if device is not None else torch.from_numpy(ts)
-        self._ts = [int(t) for t in ts]
+        self._set_sigma_schedule(ts, device)
         self.num_inference_steps = num_inference_steps
         self.model_outputs = [None] * c.solver_order
         self.lower_order_nums = 0
         self._step_index = None
-
-    def scale_model_input(self, sample, timestep=None):
-        return sample
 
     @staticmethod
     def _alpha_sigma(sigma):
@@ -132,9 +148,6 @@ class DPMSolverMultistepScheduler:
             c_d1 = 0.5 * coef / r0
         return dict(sigma_s=s_s, alpha_s=a_s, c_x=s_t / s_s, c_d0=coef, c_d1=c_d1, second_order=not first)
 
-    def index_for_timestep(self, timestep):
-        return self._ts.index(int(timestep))
-
     def step(self, model_output, timestep, sample, generator=None, return_dict=True):
         """diffusers-compatible tensor update (torch ops)."""
         if self._step_index is None:
@@ -153,7 +166,7 @@ class DPMSolverMultistepScheduler:
         return SchedulerOutput(prev_sample=prev) if return_dict else (prev,)
 
 
-class DDIMScheduler:
+class DDIMScheduler(_Scheduler):
     """diffusers==0.24.0 DDIMScheduler, restated from memory like the rest of this file (diffusers is not a dependency): the
     scheduler the checkpoints of this model family carry in `scheduler/scheduler_config.json` and the one the reference's app
     samples with (reference app.py:64-113, start latents from utils/common.py:22-30 which reads `scheduler.alphas`).
@@ -163,7 +176,6 @@ class DDIMScheduler:
     thresholding and zero-SNR beta rescaling are not implemented.  The argument defaults are the values those checkpoints
     ship (scaled_linear 0.00085-0.012, no clipping, set_alpha_to_one=False, steps_offset=1), like the sibling classes, not
     diffusers' own; a `scheduler_config.json` written by diffusers names every key, so `from_config` is unaffected."""
-    order = 1
 
     def __init__(self, num_train_timesteps=1000, beta_start=0.00085, beta_end=0.012, beta_schedule="scaled_linear",
                  clip_sample=False, set_alpha_to_one=False, steps_offset=1, prediction_type="epsilon", thresholding=False,
@@ -190,12 +202,6 @@ class DDIMScheduler:
         self.timesteps = torch.from_numpy(np.arange(0, num_train_timesteps)[::-1].copy().astype(np.int64))
         self._ts = [int(t) for t in self.timesteps]
 
-    @classmethod
-    def from_config(cls, config, **overrides):
-        cfg = dict(vars(config)) if isinstance(config, SimpleNamespace) else dict(config)
-        cfg.update(overrides)
-        return cls(**{k: v for k, v in cfg.items() if not k.startswith("_")})
-
     def set_timesteps(self, num_inference_steps, device=None):
         c, N, n = self.config, self.config.num_train_timesteps, int(num_inference_steps)
         if not 0 < n <= N:
@@ -210,18 +216,7 @@ class DDIMScheduler:
         self._ts = [int(t) for t in ts]
         self.num_inference_steps = n
 
-    def scale_model_input(self, sample, timestep=None):
-        return sample
-
-    def add_noise(self, original_samples, noise, timesteps):
-        acp = self.alphas_cumprod.to(original_samples.device)[torch.as_tensor(timesteps).to(original_samples.device).long()]
-        shape = (-1,) + (1,) * (original_samples.dim() - 1)
-        a = acp.sqrt().reshape(shape).to(original_samples.dtype)
-        s = (1 - acp).sqrt().reshape(shape).to(original_samples.dtype)
-        return a * original_samples + s * noise
-
-    def index_for_timestep(self, timestep):
-        return self._ts.index(int(timestep))
+    add_noise = DDPMScheduler.add_noise
 
     # ---- scalar part of one step (shared by `step` and the fused kernel) -------------------------
     def _coefficients_at(self, t: int, eta: float, use_clipped_model_output: bool):
@@ -269,7 +264,7 @@ class DDIMScheduler:
         return SchedulerOutput(prev_sample=prev, pred_original_sample=x0) if return_dict else (prev,)
 
 
-class UniPCMultistepScheduler:
+class UniPCMultistepScheduler(_Scheduler):
     """diffusers==0.24.0 UniPCMultistepScheduler (Zhao et al. 2023, "UniPC: a unified predictor-corrector framework"), restated
     like the rest of this file (diffusers is not a dependency): a multistep predictor of order `solver_order` in the
     data-prediction form plus a corrector that re-uses the model output of the NEXT step to raise the order by one - no
@@ -280,7 +275,6 @@ class UniPCMultistepScheduler:
     schedule-dependent part is host float64 math (`scalars`, `coefficients`); the tensor update is either the torch
     expression of `step()` (fp32) or the fused HIP kernel `aa_cfg_unipc_step_tokens`.  Dynamic thresholding, Karras sigmas,
     the noise-prediction form (`predict_x0=False`) and `solver_p` are not implemented."""
-    order = 1
 
     def __init__(self, num_train_timesteps=1000, beta_start=0.00085, beta_end=0.012, beta_schedule="scaled_linear",
                  solver_order=2, prediction_type="epsilon", thresholding=False, predict_x0=True, solver_type="bh2",
@@ -305,18 +299,12 @@ class UniPCMultistepScheduler:
                                       lower_order_final=lower_order_final, disable_corrector=tuple(disable_corrector),
                                       solver_p=solver_p, use_karras_sigmas=use_karras_sigmas,
                                       timestep_spacing=timestep_spacing, steps_offset=steps_offset)
-        self._acp = np.cumprod(1.0 - _betas(num_train_timesteps, beta_start, beta_end, beta_schedule))
+        self._acp = _alphas_cumprod(num_train_timesteps, beta_start, beta_end, beta_schedule)
         self.alphas_cumprod = torch.from_numpy(self._acp)
         self.init_noise_sigma = 1.0
         self.disable_corrector = tuple(disable_corrector)
         self.timesteps = None
         self.sigmas = None
-
-    @classmethod
-    def from_config(cls, config, **overrides):
-        cfg = dict(vars(config)) if isinstance(config, SimpleNamespace) else dict(config)
-        cfg.update(overrides)
-        return cls(**{k: v for k, v in cfg.items() if not k.startswith("_")})
 
     def set_timesteps(self, num_inference_steps, device=None):
         c, N, n = self.config, self.config.num_train_timesteps, int(num_inference_steps)
@@ -329,11 +317,7 @@ class UniPCMultistepScheduler:
             ts = np.round(np.arange(N, 0, -N / n)).astype(np.int64) - 1
         if len(set(ts.tolist())) != len(ts):
             raise ValueError(f"{n} steps with {c.timestep_spacing!r} spacing repeat a timestep: the multistep history needs distinct ones")
-        sig = ((1 - self._acp) / self._acp) ** 0.5
-        sigmas = np.concatenate([np.interp(ts, np.arange(N), sig), [sig[0]]]).astype(np.float32)
-        self.sigmas = sigmas.astype(np.float64)
-        self.timesteps = torch.from_numpy(ts).to(device) if device is not None else torch.from_numpy(ts)
-        self._ts = [int(t) for t in ts]
+        self._set_sigma_schedule(ts, device)
         self.num_inference_steps = n
         self.model_outputs = [None] * 3                     # m_{i-3}, m_{i-2}, m_{i-1}
         self.last_sample = None
@@ -341,14 +325,8 @@ class UniPCMultistepScheduler:
         self._steps_done = 0
         self._step_index = None
 
-    def scale_model_input(self, sample, timestep=None):
-        return sample
-
     _alpha_sigma = staticmethod(DPMSolverMultistepScheduler._alpha_sigma)
     add_noise = DPMSolverMultistepScheduler.add_noise
-
-    def index_for_timestep(self, timestep):
-        return self._ts.index(int(timestep))
 
     # ---- scalar part of one step (shared by `step` and the fused kernel) -------------------------
     @staticmethod
@@ -466,7 +444,7 @@ class UniPCMultistepScheduler:
         return SchedulerOutput(prev_sample=prev, pred_original_sample=m.to(sample.dtype)) if return_dict else (prev,)
 
 
-class EulerDiscreteScheduler:
+class EulerDiscreteScheduler(_Scheduler):
     """diffusers==0.24.0 EulerDiscreteScheduler in the configuration Stable Video Diffusion ships (the scheduler the
     reference's SVD pipelines drive: /root/reference/models/pipeline.py:399-401 set_timesteps, :419 scale_model_input,
     :440 step; /root/reference/train_svd.py:732-733): v-prediction, Karras sigmas between sigma_min and sigma_max,
@@ -474,7 +452,6 @@ class EulerDiscreteScheduler:
 
     The schedule is host math (float64, sigmas rounded to float32 like diffusers); the tensor update is either the torch
     expression of `step()` or the fused HIP kernel `aa_cfg_euler_step_tokens` fed by `coefficients()`."""
-    order = 1
 
     def __init__(self, num_train_timesteps=1000, beta_start=0.00085, beta_end=0.012, beta_schedule="scaled_linear",
                  prediction_type="v_prediction", interpolation_type="linear", use_karras_sigmas=True, sigma_min=0.002,
@@ -486,17 +463,11 @@ class EulerDiscreteScheduler:
                                       interpolation_type=interpolation_type, use_karras_sigmas=use_karras_sigmas,
                                       sigma_min=sigma_min, sigma_max=sigma_max, timestep_spacing=timestep_spacing,
                                       timestep_type=timestep_type, steps_offset=steps_offset)
-        acp = np.cumprod(1.0 - _betas(num_train_timesteps, beta_start, beta_end, beta_schedule))
+        acp = _alphas_cumprod(num_train_timesteps, beta_start, beta_end, beta_schedule)
         self._train_sigmas = ((1 - acp) / acp) ** 0.5
         self.timesteps = None
         self.sigmas = None
         self._step_index = None
-
-    @classmethod
-    def from_config(cls, config, **overrides):
-        cfg = dict(vars(config)) if isinstance(config, SimpleNamespace) else dict(config)
-        cfg.update(overrides)
-        return cls(**{k: v for k, v in cfg.items() if not k.startswith("_")})
 
     def set_timesteps(self, num_inference_steps, device=None):
         c = self.config
