@@ -7,6 +7,7 @@
 #include <stdarg.h>
 #include <stdio.h>
 #include <stdlib.h>
+#include <string.h>
 #include "aa_mi355.h"
 #include "kernels/conv_gemm.h"
 #include "kernels/conv_gemm_dma.h"
@@ -20,6 +21,7 @@
 #include "kernels/linear_fp8.h"
 #include "kernels/glue.h"
 #include "kernels/freeu.h"
+#include "kernels/cfg_rescale.h"
 
 namespace aa {
 
@@ -1139,6 +1141,63 @@ int aa_freeu_tokens(const AaFreeU* d, void* stream) {
     if (d->dtype == AA_F16) AA_LAUNCH((freeu_tok_kernel<f16_t>), grid, block, FU_LDS_BYTES, stream, *d);
     else AA_LAUNCH((freeu_tok_kernel<bf16_t>), grid, block, FU_LDS_BYTES, stream, *d);
     return finish("freeu_tokens");
+}
+
+// (a test on the stored bits, never on a float VALUE: the library is built with -ffast-math, under which the compiler takes every float
+//  value for finite and folds isfinite - and a bit test behind a float parameter - away)
+static bool finite_f32(const float* v) {
+    uint32_t bits;
+    memcpy(&bits, v, 4);
+    return (bits & 0x7f800000u) != 0x7f800000u;
+}
+
+static bool cfg_rescale_geometry_ok(const AaCfgRescale* d) {
+    if (d->clips < 1 || d->channels < 1 || d->frames < 1 || d->hw < 1 || d->clips > 65535) return false;
+    if ((int64_t)d->channels * d->frames * d->hw < 2) return false;
+    return (int64_t)2 * d->clips * ((int64_t)d->frames + 1) * d->hw < ((int64_t)1 << 31);
+}
+
+size_t aa_cfg_rescale_workspace(const AaCfgRescale* d) {
+    if (!d || !cfg_rescale_geometry_ok(d)) return 0;
+    return (size_t)d->clips * aa::cr_parts(*d) * 4 * sizeof(double);
+}
+
+int aa_cfg_rescale_tokens(const AaCfgRescale* d, void* workspace, size_t workspace_bytes, void* stream) {
+    using namespace aa;
+    if (!d || !d->tokens || !d->out) return fail(AA_E_SHAPE, "cfg_rescale_tokens: null operand");
+    if (!cfg_rescale_geometry_ok(d))
+        return fail(AA_E_SHAPE, "cfg_rescale_tokens: bad geometry (clips %d, channels %d, frames %d, hw %d; at least two elements per clip)",
+                    d->clips, d->channels, d->frames, d->hw);
+    if (d->ld < d->channels || d->out_ld < d->channels) return fail(AA_E_SHAPE, "cfg_rescale_tokens: a row pitch is smaller than the channel count");
+    if (!finite_f32(&d->rescale) || d->rescale < 0.0f || d->rescale > 1.0f) return fail(AA_E_SHAPE, "cfg_rescale_tokens: rescale must lie in [0, 1]");
+    if (!finite_f32(&d->guidance)) return fail(AA_E_SHAPE, "cfg_rescale_tokens: guidance must be finite");
+    if (d->dtype != AA_F16 && d->dtype != AA_BF16) return fail(AA_E_DTYPE, "cfg_rescale_tokens: unsupported dtype %d", d->dtype);
+    const size_t need = aa_cfg_rescale_workspace(d);
+    if (!workspace || workspace_bytes < need) return fail(AA_E_WORKSPACE, "cfg_rescale_tokens: workspace %zu < %zu bytes", workspace_bytes, need);
+    if ((reinterpret_cast<uintptr_t>(d->tokens) & 1) || (reinterpret_cast<uintptr_t>(d->out) & 1) || (reinterpret_cast<uintptr_t>(d->factor) & 3) ||
+        (reinterpret_cast<uintptr_t>(workspace) & 7))
+        return fail(AA_E_ALIGN, "cfg_rescale_tokens: tokens / out must be 2-byte, factor 4-byte, the workspace 8-byte aligned");
+    const int64_t rows = (int64_t)d->clips * (d->frames + 1) * d->hw;
+    struct Span { const char* p; int64_t bytes; };
+    const Span sp[4] = {{(const char*)d->tokens, ((2 * rows - 1) * d->ld + d->channels) * 2}, {(const char*)d->out, ((rows - 1) * d->out_ld + d->channels) * 2},
+                        {(const char*)d->factor, d->factor ? (int64_t)d->clips * 4 : 0}, {(const char*)workspace, (int64_t)need}};
+    for (int i = 0; i < 4; ++i)
+        for (int j = i + 1; j < 4; ++j) {
+            if (!(sp[i].p < sp[j].p + sp[j].bytes && sp[j].p < sp[i].p + sp[i].bytes)) continue;
+            if (i == 0 && j == 1 && d->tokens == d->out && d->ld == d->out_ld) continue;
+            return fail(AA_E_SHAPE, i == 0 && j == 1 ? "cfg_rescale_tokens: out may be the unconditional half of tokens (same pointer and pitch) or a separate buffer, not overlap it"
+                                                     : "cfg_rescale_tokens: factor and the workspace must not overlap the matrices or each other");
+        }
+    const dim3 grid((unsigned)cr_parts(*d), (unsigned)d->clips), block(CR_THREADS);
+    double* ws = (double*)workspace;
+    if (d->dtype == AA_F16) {
+        AA_LAUNCH((cfg_rescale_moments_kernel<f16_t>), grid, block, CR_LDS_BYTES, stream, *d, ws);
+        AA_LAUNCH((cfg_rescale_apply_kernel<f16_t>), grid, block, CR_LDS_BYTES, stream, *d, (const double*)ws);
+    } else {
+        AA_LAUNCH((cfg_rescale_moments_kernel<bf16_t>), grid, block, CR_LDS_BYTES, stream, *d, ws);
+        AA_LAUNCH((cfg_rescale_apply_kernel<bf16_t>), grid, block, CR_LDS_BYTES, stream, *d, (const double*)ws);
+    }
+    return finish("cfg_rescale_tokens");
 }
 
 }  // extern "C"

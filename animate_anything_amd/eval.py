@@ -6,7 +6,8 @@
 Same YAML keys and dot-list overrides (`pretrained_model_path`, `validation_data.{prompt,prompt_image,mask,strength,
 num_frames,width,height,num_inference_steps,guidance_scale,fps}`, `seed`, `motion_mask`, `motion_strength`), plus
 `sampler: ddim` for the checkpoint's own DDIM scheduler or `sampler: unipc` for UniPC (the sampler for 8-12 steps) in place
-of DPM-Solver++, and `freeu: {s1: .., s2: .., b1: .., b2: ..}` for diffusers' FreeU switch.
+of DPM-Solver++, `freeu: {s1: .., s2: .., b1: .., b2: ..}` for diffusers' FreeU switch and `validation_data.guidance_rescale`
+(a number in [0, 1], absent = 0) for diffusers' `guidance_rescale`.
 The third-party pieces the reference pulls in and that do not exist in this image are replaced by small
 equivalents: OmegaConf -> PyYAML + dot-list merge, `VaeImageProcessor.preprocess` -> PIL lanczos resize + [-1,1]
 scaling, torchvision `ToTensor`/`Resize(antialias=False)` -> torch bilinear interpolate, imageio -> PIL GIF writer.
@@ -191,7 +192,8 @@ def eval(pipeline, validation_data, out_file, index, forward_t=25, preview=True,
             latents=initial_latents, width=validation_data.width, height=validation_data.height,
             num_frames=validation_data.num_frames, num_inference_steps=validation_data.num_inference_steps,
             guidance_scale=validation_data.guidance_scale, condition_latent=input_image_latents, mask=mask,
-            motion=[motion_strength], return_dict=False, timesteps=timesteps, **prompt_kwargs)
+            motion=[motion_strength], return_dict=False, timesteps=timesteps,
+            guidance_rescale=_check_guidance_rescale(validation_data), **prompt_kwargs)
     if preview:
         save_gif(out_file, video_frames, validation_data.get("fps", 8))
     real_motion_strength = calculate_latent_motion_score(video_latents.float()).cpu().numpy()[0]
@@ -223,6 +225,14 @@ def _check_freeu(freeu):
     return {k: float(freeu[k]) for k in FREEU_KEYS}
 
 
+def _check_guidance_rescale(validation_data):
+    """`validation_data.guidance_rescale`: absent (0.0) or a number in [0, 1]; returns it as a float."""
+    r = validation_data.get("guidance_rescale", 0.0) if validation_data is not None else 0.0
+    if isinstance(r, bool) or not isinstance(r, (int, float)) or not 0.0 <= r <= 1.0:
+        raise ValueError(f"validation_data.guidance_rescale = {r!r}: a number in [0, 1]")
+    return float(r)
+
+
 def batch_eval(unet, text_encoder, vae, tokenizer, scheduler_config, validation_data, output_dir, preview,
                global_step=0, iters=6, generator=None, indices=None, seed=None, lora_path=None, lora_rank=16,
                unet_lora_modules=("UNet3DConditionModel",), guidance_group=None, sampler="dpm"):
@@ -232,6 +242,7 @@ def batch_eval(unet, text_encoder, vae, tokenizer, scheduler_config, validation_
     `indices` (clip sharding, main_eval): render only these sample indices, each with its own generator seeded
     `seed + index` (distributed.clip_seed) so that a sample does not depend on which rank renders it."""
     _check_sampler(sampler)
+    _check_guidance_rescale(validation_data)
     unet.eval()
     scheduler = SAMPLERS[sampler].from_config(scheduler_config)
     pipeline = LatentToVideoPipeline(vae=vae, text_encoder=text_encoder, tokenizer=tokenizer, unet=unet,
@@ -268,6 +279,7 @@ def main_eval(pretrained_model_path, validation_data, seed=None, motion_mask=Non
     outputs do not depend on W) and the final latents are all-gathered over RCCL (distributed.gather_clips)."""
     _check_sampler(sampler)                               # (before any model is loaded)
     freeu = _check_freeu(freeu)
+    _check_guidance_rescale(validation_data)
     from . import distributed as D
     rank, world, _dev = D.init()
     generator = None

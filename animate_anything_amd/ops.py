@@ -17,7 +17,7 @@ import torch
 
 from . import _lib
 from ._lib import (AA_ACT_GELU, AA_ACT_NONE, AA_ACT_QUICK_GELU, AA_ACT_SILU, AA_BF16, AA_F16, AA_F32, AaAttention, AaAttnOperand,
-                   AaBlend, AaConvGemm, AaFFFused, AaLinearRows, AaLinearFp8, AaQuantRowsFp8, AaDdimStepTok, AaDpmStep, AaDpmStepTok, AaEulerStepTok, AaGroupNorm, AaPackFrames, AaPackLatents, AaSeqSelfAttn, AaUnipcStepTok, AaFreeU)
+                   AaBlend, AaConvGemm, AaFFFused, AaLinearRows, AaLinearFp8, AaQuantRowsFp8, AaDdimStepTok, AaDpmStep, AaDpmStepTok, AaEulerStepTok, AaGroupNorm, AaPackFrames, AaPackLatents, AaSeqSelfAttn, AaUnipcStepTok, AaFreeU, AaCfgRescale)
 
 _DT = {torch.float16: AA_F16, torch.bfloat16: AA_BF16, torch.float32: AA_F32}
 
@@ -1388,3 +1388,47 @@ def freeu(hidden: torch.Tensor, skip: torch.Tensor, images: int, h: int, w: int,
     d.b, d.s, d.dtype = float(b), float(s), _DT[hidden.dtype]
     _run(lib.aa_freeu_tokens, C.byref(d), _stream(hidden))
     return ho, so
+
+
+# ------------------------------------------------------------------------------------- guidance rescale
+_CFG_RESCALE_WS = {}
+
+
+def cfg_rescale_tokens(tokens: torch.Tensor, clips: int, channels: int, frames: int, hw: int, guidance: float, rescale: float,
+                       out: Optional[torch.Tensor] = None, factor: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """guidance_rescale (diffusers `rescale_noise_cfg`, per clip) on the UNet's token-layout output `tokens`
+    [2*clips*(frames+1)*hw, >= channels] (unconditional clips first; rows may be pitched: stride(0) >= channels, stride(1) == 1):
+    k_b * (u + guidance * (t - u)) with k_b = 1 + rescale * (std(t) / std(u + guidance * (t - u)) - 1) over frames 1..frames and columns
+    [0, channels) of clip b, written to `out` [clips*(frames+1)*hw, >= channels] - None: in place, over the unconditional half of
+    `tokens` - for the step kernel to read with guidance off (aa_cfg_rescale_tokens: two launches).  `factor`: fp32 [clips], receives
+    k_b.  A constant guided clip keeps k_b = 1 (diffusers: NaN).  The fp64 workspace is kept per (device, geometry).  Returns `out`."""
+    lib = _lib.get()
+    clips, channels, frames, hw = int(clips), int(channels), int(frames), int(hw)
+    rows = clips * (frames + 1) * hw
+    if out is None:
+        out = tokens[:max(rows, 0)] if tokens.dim() == 2 else tokens
+    for name, t, need in (("tokens", tokens, 2 * rows), ("out", out, rows)):
+        if not t.is_cuda and not _lib.host_pointers_ok():
+            raise RuntimeError("animate_anything_amd ops run on the GPU only (tensor is on %s)" % t.device)
+        if t.dim() != 2 or (t.shape[1] > 1 and t.stride(1) != 1) or t.dtype != tokens.dtype or t.dtype not in (torch.float16, torch.bfloat16):
+            raise RuntimeError(f"cfg_rescale_tokens: {name} must be a 2-d fp16 / bf16 token matrix with contiguous rows, both of one dtype")
+        if t.device != tokens.device:
+            raise RuntimeError(f"cfg_rescale_tokens: {name} is on {t.device}, tokens on {tokens.device}")
+        if min(clips, channels, frames, hw) >= 1 and (t.shape[0] < need or t.shape[1] < channels):
+            raise RuntimeError(f"cfg_rescale_tokens: {name} {tuple(t.shape)} does not hold {need} rows of {channels} channels")
+    if factor is not None:
+        _check(factor)
+        if factor.dtype != torch.float32 or factor.numel() != max(clips, 0) or factor.device != tokens.device:
+            raise RuntimeError("cfg_rescale_tokens: factor must be fp32 [clips] on the tokens' device")
+    d = AaCfgRescale()
+    d.tokens, d.out, d.factor = _ptr(tokens), _ptr(out), _ptr(factor)
+    d.clips, d.channels, d.frames, d.hw = clips, channels, frames, hw
+    d.ld, d.out_ld = tokens.stride(0), out.stride(0)
+    d.guidance, d.rescale, d.dtype = float(guidance), float(rescale), _DT[tokens.dtype]
+    nbytes = lib.aa_cfg_rescale_workspace(C.byref(d))
+    key = (str(tokens.device), clips, channels, frames, hw)
+    ws = _CFG_RESCALE_WS.get(key)
+    if ws is None or ws.numel() * 8 < nbytes:
+        ws = _CFG_RESCALE_WS[key] = torch.empty(max(nbytes // 8, 1), dtype=torch.float64, device=tokens.device)
+    _run(lib.aa_cfg_rescale_tokens, C.byref(d), _ptr(ws), ws.numel() * 8, _stream(tokens))
+    return out

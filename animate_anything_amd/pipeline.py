@@ -77,6 +77,29 @@ def calculate_latent_motion_score(latents):
     return diff.mean(dim=[2, 3, 4]).sum(dim=1) * 10
 
 
+def rescale_noise_cfg(noise_cfg, noise_pred_text, guidance_rescale=0.0):
+    """diffusers `rescale_noise_cfg` (Lin et al., "Common Diffusion Noise Schedules and Sample Steps are Flawed", section 3.4): the guided
+    prediction scaled per sample to the deviation of the text prediction, blended with weight `guidance_rescale`; evaluated in fp32
+    (float64 operands stay float64).  guidance_rescale = 0 returns `noise_cfg` itself.  A sample whose guided prediction is constant
+    (deviation 0: NaN in diffusers) is left unscaled, as aa_cfg_rescale_tokens leaves it."""
+    if guidance_rescale == 0:
+        return noise_cfg
+    wide = torch.float64 if noise_cfg.dtype == torch.float64 else torch.float32
+    cfg, text = noise_cfg.to(wide), noise_pred_text.to(wide)
+    dims = list(range(1, cfg.dim()))
+    std_text, std_cfg = text.std(dim=dims, keepdim=True), cfg.std(dim=dims, keepdim=True)
+    ratio = torch.where(std_cfg > 0, std_text / std_cfg, torch.ones_like(std_cfg))
+    noise_pred_rescaled = cfg * ratio
+    return guidance_rescale * noise_pred_rescaled + (1 - guidance_rescale) * cfg
+
+
+def _check_guidance_rescale(guidance_rescale):
+    r = float(guidance_rescale)
+    if not 0.0 <= r <= 1.0:                                   # (NaN fails both comparisons)
+        raise ValueError(f"guidance_rescale {guidance_rescale!r}: a number in [0, 1]")
+    return r
+
+
 def tensor2vid(video):
     """diffusers 0.24 tensor2vid (mean = std = 0.5): [b,c,f,h,w] -> list of f uint8 [h, b*w, c] frames."""
     video = (video.float() * 0.5 + 0.5).clamp(0, 1)
@@ -199,7 +222,7 @@ class LatentToVideoPipeline:
 
     # ------------------------------------------------------------------ denoising
     def denoise(self, latents, prompt_embeds, condition_latent, mask, motion, timesteps, guidance_scale,
-                callback=None, callback_steps=1, eta=0.0, generator=None):
+                callback=None, callback_steps=1, eta=0.0, generator=None, guidance_rescale=0.0):
         """The hot loop (reference pipeline.py:163-198).  `prompt_embeds` already holds [uncond; text]
         when guidance is on.  Latents are kept in fp32.
 
@@ -209,13 +232,17 @@ class LatentToVideoPipeline:
         the session's `sample` input, duplicated for guidance by the packing kernel - and deposits the next timestep.
         `eta` / `generator` reach the scheduler as in the reference (pipeline.py:156,189): DDIM with eta > 0 adds one
         torch.randn per step, DPM-Solver++ and UniPC take neither.  UniPC keeps four fp32 buffers of the latents' size for
-        the length of the call (the corrected sample and three data predictions)."""
+        the length of the call (the corrected sample and three data predictions).
+        `guidance_rescale` > 0 under guidance (diffusers' argument, `rescale_noise_cfg`): the step becomes session run,
+        ops.cfg_rescale_tokens - the rescaled guided prediction written over the unconditional half of the token matrix, two
+        launches - and the same solver kernel with guidance off.  With 0, the default, a step issues what it issued before."""
         cfg = guidance_scale > 1.0
+        rescale = _check_guidance_rescale(guidance_rescale) if cfg else 0.0
         sched = self.scheduler
         unet = self.unet
         if not (isinstance(sched, (DPMSolverMultistepScheduler, DDIMScheduler, UniPCMultistepScheduler)) and hasattr(unet, "session")):
             return self._denoise_generic(latents, prompt_embeds, condition_latent, mask, motion, timesteps, guidance_scale,
-                                         callback, callback_steps, eta, generator)
+                                         callback, callback_steps, eta, generator, guidance_rescale=guidance_rescale)
         dev = latents.device
         b0, _, frames, h, w = latents.shape
         use_mask = bool(unet.motion_mask and mask is not None)
@@ -248,8 +275,12 @@ class LatentToVideoPipeline:
                   t=torch.full((b,), float(ts[0]) if ts else 0.0, dtype=torch.float32, device=dev))
         x = sess.inputs["sample"]                               # fp32 [b0,C,T,h,w]: updated in place by the solver kernel
         step = self._solver_step(x, eta, generator)
+        guidance = guidance_scale if cfg else None
         for i, t in enumerate(ts):
-            step(tokens(), guidance_scale if cfg else None, t, i, sess.inputs["t"], float(ts[i + 1]) if i + 1 < len(ts) else float(t))
+            tok = tokens()
+            if rescale > 0.0:                                   # in place: the next session run (or gather) rewrites the matrix
+                ops.cfg_rescale_tokens(tok, b0, x.shape[1], frames, h * w, guidance_scale, rescale)
+            step(tok, None if rescale > 0.0 else guidance, t, i, sess.inputs["t"], float(ts[i + 1]) if i + 1 < len(ts) else float(t))
             if callback is not None and i % callback_steps == 0:
                 callback(i, t, x)
         return x.clone()
@@ -289,13 +320,15 @@ class LatentToVideoPipeline:
         return [torch.zeros_like(x) for _ in range(4)]
 
     def _denoise_generic(self, latents, prompt_embeds, condition_latent, mask, motion, timesteps, guidance_scale,
-                         callback=None, callback_steps=1, eta=0.0, generator=None):
+                         callback=None, callback_steps=1, eta=0.0, generator=None, guidance_rescale=0.0):
         """Any scheduler with a diffusers-style `step()`: the UNet through its module `forward`, guidance and the update as
         torch expressions (the reference's own sequence, pipeline.py:165-192).  `eta` / `generator` go to a `step()` that
         names them (diffusers' prepare_extra_step_kwargs, pipeline.py:156); DDIM's variance noise is drawn here exactly as
-        the fused loop draws it, so both consume the generator alike."""
+        the fused loop draws it, so both consume the generator alike.  `guidance_rescale` > 0 under guidance applies
+        `rescale_noise_cfg` to the guided prediction."""
         import inspect
         cfg = guidance_scale > 1.0
+        rescale = _check_guidance_rescale(guidance_rescale) if cfg else 0.0
         dt = self.unet.dtype
         sched = self.scheduler
         accepted = set(inspect.signature(sched.step).parameters)
@@ -313,6 +346,8 @@ class LatentToVideoPipeline:
                             motion=None if motion is None else torch.as_tensor(motion, device=x.device)).sample
             e_u, e_t = (eps[: x.shape[0]], eps[x.shape[0]:]) if cfg else (eps, eps)
             e = e_u.float() + guidance_scale * (e_t.float() - e_u.float()) if cfg else eps.float()
+            if rescale > 0.0:
+                e = rescale_noise_cfg(e, e_t.float(), rescale)
             b, c, f, h, w = x.shape
             if isinstance(sched, DDIMScheduler) and eta > 0:
                 extra["variance_noise"] = _variance_noise(x, generator)
@@ -328,7 +363,7 @@ class LatentToVideoPipeline:
                  guidance_scale=9.0, negative_prompt=None, eta=0.0, generator=None, latents=None,
                  prompt_embeds=None, negative_prompt_embeds=None, output_type="np", return_dict=True,
                  callback=None, callback_steps=1, cross_attention_kwargs=None, condition_latent=None,
-                 mask=None, timesteps=None, motion=None):
+                 mask=None, timesteps=None, motion=None, guidance_rescale=0.0):
         if latents is None:
             raise ValueError("LatentToVideoPipeline expects caller-prepared `latents` (reference pipeline.py:153)")
         height = height or latents.shape[-2] * self.vae_scale_factor
@@ -341,7 +376,7 @@ class LatentToVideoPipeline:
         if timesteps is None:
             timesteps = self.scheduler.timesteps
         x = self.denoise(latents, prompt_embeds, condition_latent, mask, motion, [int(t) for t in timesteps],
-                         guidance_scale, callback, callback_steps, eta=eta, generator=generator)
+                         guidance_scale, callback, callback_steps, eta=eta, generator=generator, guidance_rescale=guidance_rescale)
         latents = x.to(self.unet.dtype)
         if self.vae is None or output_type == "latent":
             video = None

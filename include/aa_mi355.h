@@ -684,6 +684,37 @@ typedef struct AaFreeU {
 
 int aa_freeu_tokens(const AaFreeU* d, void* stream);
 
+/* aa_cfg_rescale_tokens: guidance_rescale (Lin et al., "Common Diffusion Noise Schedules and Sample Steps are Flawed", section 3.4;
+ * diffusers `rescale_noise_cfg`) on the UNet's token-layout output, per clip b of the guided batch:
+ *   c   = u + guidance * (t - u)                       fp32, as the step kernels form it (u: unconditional clip b, t: text clip b)
+ *   k_b = 1 + rescale * (std(t) / std(c) - 1)          unbiased deviations over the n = channels * frames * hw elements the step kernels
+ *                                                      consume: frames 1..frames of the clip, columns [0, channels)
+ *   out = k_b * c                                      rounded once to the storage type
+ * `tokens` is [2 * clips * (frames + 1) * hw][ld], the unconditional clips first; `out` is [clips * (frames + 1) * hw][out_ld], a separate
+ * buffer or exactly the unconditional half of `tokens` (same pointer, same pitch: in place).  Frame-0 rows and columns >= channels of
+ * `out` are never written.  The step kernel then runs on `out` with guidance off.  `factor` (optional, fp32 [clips]) receives k_b.
+ * Two launches, no atomics: partial sums of t - t_0, (t - t_0)^2, c - c_0, (c - c_0)^2 (fp64; t_0, c_0 the clip's first element) per
+ * slice of a clip into the workspace, then every workgroup adds its clip's partials in a fixed order and scales its slice: a replay, a
+ * second call and the in-place form repeat the bits of an eager out-of-place call.  rescale = 0 gives k_b = 1 exactly.
+ * DEPARTURE from diffusers: std(c) == 0 (a constant guided clip) is NaN there; here k_b = 1 and the prediction is left unscaled.
+ * Refused with nothing launched - AA_E_SHAPE: a null descriptor, tokens or out; clips, channels, frames or hw < 1; n < 2; a pitch smaller
+ * than channels; more than 65535 clips or 2^31 token rows; rescale not finite or outside [0, 1]; guidance not finite; an `out` that
+ * overlaps `tokens` other than as the identical unconditional half; a `factor` or workspace that overlaps either matrix or each other.
+ * AA_E_WORKSPACE: a null or too small workspace (aa_cfg_rescale_workspace(d) bytes).  AA_E_ALIGN: tokens / out not 2-byte, factor not
+ * 4-byte, workspace not 8-byte aligned.  AA_E_DTYPE: a dtype other than AA_F16 / AA_BF16. */
+typedef struct AaCfgRescale {
+    const void* tokens;       /* [2 * clips * (frames + 1) * hw][ld] */
+    void* out;                /* [clips * (frames + 1) * hw][out_ld] */
+    float* factor;            /* fp32 [clips] or NULL */
+    int32_t clips, channels, frames, hw;
+    int32_t ld, out_ld;       /* row pitches in elements (>= channels; 4 is legal) */
+    float guidance, rescale;
+    int32_t dtype;            /* AA_F16 / AA_BF16 */
+} AaCfgRescale;
+
+size_t aa_cfg_rescale_workspace(const AaCfgRescale* d);
+int aa_cfg_rescale_tokens(const AaCfgRescale* d, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
