@@ -192,11 +192,38 @@ class AaCfgRescale(C.Structure):
     ]
 
 
+AA_WINDOW_MAX = 64
+
+
+class AaWindow(C.Structure):
+    _fields_ = [
+        ("window_frames", C.c_int32), ("frame", C.c_int32 * AA_WINDOW_MAX), ("weight", C.c_float * AA_WINDOW_MAX),
+        ("first", C.c_int32 * AA_WINDOW_MAX), ("last", C.c_int32 * AA_WINDOW_MAX),
+    ]
+
+
+class AaWindowGather(C.Structure):
+    _fields_ = [
+        ("src", C.c_void_p), ("dst", C.c_void_p),
+        ("clips", C.c_int32), ("channels", C.c_int32), ("total_frames", C.c_int32), ("hw", C.c_int32),
+        ("window", AaWindow),
+    ]
+
+
+class AaWindowMerge(C.Structure):
+    _fields_ = [
+        ("tokens", C.c_void_p), ("acc", C.c_void_p), ("merged", C.c_void_p),
+        ("clips", C.c_int32), ("channels", C.c_int32), ("total_frames", C.c_int32), ("hw", C.c_int32), ("ld", C.c_int32), ("out_ld", C.c_int32),
+        ("guidance_on", C.c_int32), ("guidance", C.c_float), ("dtype", C.c_int32),
+        ("window", AaWindow),
+    ]
+
+
 SYMBOLS = ("aa_version", "aa_last_error", "aa_set_tile_override", "aa_conv_gemm_tile_info", "aa_conv_gemm_tile_ok", "aa_conv_gemm_workspace", "aa_conv_gemm", "aa_conv_gemm_launch_count", "aa_conv_gemm_row_stats_parts", "aa_conv_gemm_row_coef_ok", "aa_conv_gemm_tickets", "aa_conv_gemm_reduce_launches", "aa_conv_gemm_tile_flags", "aa_ln_finalize", "aa_groupnorm_workspace", "aa_groupnorm", "aa_groupnorm_coef", "aa_set_groupnorm_two_pass", "aa_groupnorm_plan",
            "aa_layernorm", "aa_attention", "aa_seq_self_attention_ok", "aa_seq_self_attention", "aa_ff_fused_ok", "aa_ff_fused", "aa_linear_rows_ok", "aa_linear_rows", "aa_quant_rows_fp8", "aa_linear_fp8", "aa_softmax_rows", "aa_cfg_dpm_step",
            "aa_timestep_embedding", "aa_pack_latents", "aa_cfg_dpm_step_tokens",
            "aa_blend", "aa_pack_frames", "aa_cfg_euler_step_tokens", "aa_cfg_ddim_step_tokens", "aa_cfg_unipc_step_tokens", "aa_freeu_tokens",
-           "aa_cfg_rescale_workspace", "aa_cfg_rescale_tokens")
+           "aa_cfg_rescale_workspace", "aa_cfg_rescale_tokens", "aa_window_gather_latents", "aa_window_merge_tokens")
 
 DEFAULT_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libaa_mi355.so")
 
@@ -264,6 +291,8 @@ def bind(path: str) -> C.CDLL:
     lib.aa_cfg_rescale_workspace.argtypes = [C.POINTER(AaCfgRescale)]
     lib.aa_cfg_rescale_workspace.restype = C.c_size_t
     lib.aa_cfg_rescale_tokens.argtypes = [C.POINTER(AaCfgRescale), C.c_void_p, C.c_size_t, C.c_void_p]
+    lib.aa_window_gather_latents.argtypes = [C.POINTER(AaWindowGather), C.c_void_p]
+    lib.aa_window_merge_tokens.argtypes = [C.POINTER(AaWindowMerge), C.c_void_p]
     for s in SYMBOLS[5:]:
         if s not in ("aa_groupnorm_workspace", "aa_conv_gemm_workspace", "aa_cfg_rescale_workspace"):
             getattr(lib, s).restype = C.c_int

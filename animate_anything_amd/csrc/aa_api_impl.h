@@ -22,6 +22,7 @@
 #include "kernels/glue.h"
 #include "kernels/freeu.h"
 #include "kernels/cfg_rescale.h"
+#include "kernels/window.h"
 
 namespace aa {
 
@@ -1198,6 +1199,80 @@ int aa_cfg_rescale_tokens(const AaCfgRescale* d, void* workspace, size_t workspa
         AA_LAUNCH((cfg_rescale_apply_kernel<bf16_t>), grid, block, CR_LDS_BYTES, stream, *d, (const double*)ws);
     }
     return finish("cfg_rescale_tokens");
+}
+
+// The window a context-window descriptor carries by value: slot count, frame indices in range and distinct (two slots on one frame
+// would race in the merge), and - `weights` - finite weights.  Returns the complaint or null.
+static const char* window_complaint(const AaWindow& w, int total_frames, bool weights) {
+    if (w.window_frames < 1 || w.window_frames > AA_WINDOW_MAX) return "window_frames must lie in [1, AA_WINDOW_MAX]";
+    if (w.window_frames > total_frames) return "window_frames exceeds total_frames";
+    for (int j = 0; j < w.window_frames; ++j) {
+        if (w.frame[j] < 0 || w.frame[j] >= total_frames) return "a frame index lies outside [0, total_frames)";
+        for (int i = 0; i < j; ++i)
+            if (w.frame[i] == w.frame[j]) return "a frame index is repeated inside the window";
+        if (weights && !finite_f32(&w.weight[j])) return "a weight is not finite";
+    }
+    return nullptr;
+}
+
+static bool spans_overlap(const void* a, int64_t a_bytes, const void* b, int64_t b_bytes) {
+    const char* pa = (const char*)a;
+    const char* pb = (const char*)b;
+    return pa < pb + b_bytes && pb < pa + a_bytes;
+}
+
+int aa_window_gather_latents(const AaWindowGather* d, void* stream) {
+    using namespace aa;
+    if (!d || !d->src || !d->dst) return fail(AA_E_SHAPE, "window_gather_latents: null operand");
+    if (d->clips < 1 || d->channels < 1 || d->total_frames < 1 || d->hw < 1 || (int64_t)d->clips * d->channels > 65535 ||
+        (int64_t)d->clips * d->channels * d->total_frames * d->hw >= ((int64_t)1 << 31))
+        return fail(AA_E_SHAPE, "window_gather_latents: bad geometry (clips %d, channels %d, total_frames %d, hw %d)", d->clips, d->channels,
+                    d->total_frames, d->hw);
+    if (const char* why = window_complaint(d->window, d->total_frames, false)) return fail(AA_E_SHAPE, "window_gather_latents: %s", why);
+    if ((reinterpret_cast<uintptr_t>(d->src) & 3) || (reinterpret_cast<uintptr_t>(d->dst) & 3))
+        return fail(AA_E_ALIGN, "window_gather_latents: src / dst must be 4-byte aligned");
+    const int64_t planes = (int64_t)d->clips * d->channels;
+    if (spans_overlap(d->src, planes * d->total_frames * d->hw * 4, d->dst, planes * d->window.window_frames * d->hw * 4))
+        return fail(AA_E_SHAPE, "window_gather_latents: src and dst must not overlap");
+    const bool vec = d->hw % 4 == 0 && aligned16(d->src) && aligned16(d->dst);
+    const int per_row = vec ? d->hw / 4 : d->hw;
+    const dim3 grid((unsigned)((per_row + WIN_THREADS - 1) / WIN_THREADS), (unsigned)d->window.window_frames, (unsigned)planes), block(WIN_THREADS);
+    if (vec) AA_LAUNCH((window_gather_kernel<true>), grid, block, 0, stream, *d);
+    else AA_LAUNCH((window_gather_kernel<false>), grid, block, 0, stream, *d);
+    return finish("window_gather_latents");
+}
+
+int aa_window_merge_tokens(const AaWindowMerge* d, void* stream) {
+    using namespace aa;
+    if (!d || !d->tokens || !d->acc || !d->merged) return fail(AA_E_SHAPE, "window_merge_tokens: null operand");
+    if (d->clips < 1 || d->channels < 1 || d->total_frames < 1 || d->hw < 1 || d->clips > 65535 || d->channels > WIN_MAX_CHANNELS ||
+        (int64_t)2 * d->clips * ((int64_t)d->total_frames + 1) * d->hw >= ((int64_t)1 << 31))
+        return fail(AA_E_SHAPE, "window_merge_tokens: bad geometry (clips %d, channels %d of at most %d, total_frames %d, hw %d)", d->clips,
+                    d->channels, WIN_MAX_CHANNELS, d->total_frames, d->hw);
+    if (const char* why = window_complaint(d->window, d->total_frames, true)) return fail(AA_E_SHAPE, "window_merge_tokens: %s", why);
+    if (d->ld < d->channels || d->out_ld < d->channels) return fail(AA_E_SHAPE, "window_merge_tokens: a row pitch is smaller than the channel count");
+    if (!finite_f32(&d->guidance)) return fail(AA_E_SHAPE, "window_merge_tokens: guidance must be finite");
+    if (d->dtype != AA_F16 && d->dtype != AA_BF16) return fail(AA_E_DTYPE, "window_merge_tokens: unsupported dtype %d", d->dtype);
+    if ((reinterpret_cast<uintptr_t>(d->tokens) & 1) || (reinterpret_cast<uintptr_t>(d->merged) & 1) || (reinterpret_cast<uintptr_t>(d->acc) & 3))
+        return fail(AA_E_ALIGN, "window_merge_tokens: tokens / merged must be 2-byte, acc 4-byte aligned");
+    const int64_t tok_rows = (int64_t)(d->guidance_on ? 2 : 1) * d->clips * (d->window.window_frames + 1) * d->hw;
+    const int64_t out_rows = (int64_t)(d->guidance_on ? 2 : 1) * d->clips * (d->total_frames + 1) * d->hw;     // both halves under guidance
+    const int64_t tok_bytes = ((tok_rows - 1) * d->ld + d->channels) * 2, out_bytes = ((out_rows - 1) * d->out_ld + d->channels) * 2;
+    const int64_t acc_bytes = (int64_t)d->clips * d->total_frames * d->hw * d->channels * 4;
+    if (spans_overlap(d->tokens, tok_bytes, d->merged, out_bytes) || spans_overlap(d->tokens, tok_bytes, d->acc, acc_bytes) ||
+        spans_overlap(d->merged, out_bytes, d->acc, acc_bytes))
+        return fail(AA_E_SHAPE, "window_merge_tokens: tokens, acc and merged must not overlap");
+    const bool vec = d->channels == 4 && d->ld % 4 == 0 && d->out_ld % 4 == 0 && !(reinterpret_cast<uintptr_t>(d->tokens) & 7) &&
+                     !(reinterpret_cast<uintptr_t>(d->merged) & 7) && aligned16(d->acc);
+    const dim3 grid((unsigned)((d->hw + WIN_THREADS - 1) / WIN_THREADS), (unsigned)d->window.window_frames, (unsigned)d->clips), block(WIN_THREADS);
+    if (d->dtype == AA_F16) {
+        if (vec) AA_LAUNCH((window_merge_kernel<f16_t, true>), grid, block, 0, stream, *d);
+        else AA_LAUNCH((window_merge_kernel<f16_t, false>), grid, block, 0, stream, *d);
+    } else {
+        if (vec) AA_LAUNCH((window_merge_kernel<bf16_t, true>), grid, block, 0, stream, *d);
+        else AA_LAUNCH((window_merge_kernel<bf16_t, false>), grid, block, 0, stream, *d);
+    }
+    return finish("window_merge_tokens");
 }
 
 }  // extern "C"

@@ -223,7 +223,7 @@ class MaskedLatentToVideoPipeline(LatentToVideoPipeline):
                  num_inference_steps=50, guidance_scale=9.0, negative_prompt=None, eta=0.0, generator=None, latents=None,
                  condition_latent=None, prompt_embeds=None, negative_prompt_embeds=None, output_type="np", return_dict=True,
                  callback=None, callback_steps=1, cross_attention_kwargs=None, timesteps=None, mask=None, motion=None,
-                 image_embeds=None, guidance_rescale=0.0):
+                 image_embeds=None, guidance_rescale=0.0, context=None):
         if latents is None:
             raise ValueError("MaskedLatentToVideoPipeline expects caller-prepared `latents`")
         height = height or latents.shape[-2] * self.vae_scale_factor
@@ -235,7 +235,8 @@ class MaskedLatentToVideoPipeline(LatentToVideoPipeline):
         if timesteps is None:
             timesteps = self.scheduler.timesteps
         x = self.denoise(latents, prompt_embeds, condition_latent, mask, motion, [int(t) for t in timesteps], guidance_scale,
-                         callback, callback_steps, eta=eta, generator=generator, guidance_rescale=guidance_rescale)
+                         callback, callback_steps, eta=eta, generator=generator, guidance_rescale=guidance_rescale,
+                         context=context)
         latents = x.to(self.unet.dtype)
         video_tensor = self.decode_latents(latents)
         pngs, alpha_jpg, pngs_rgb = decode_rgba(video_tensor, latents, vae_alpha_decoder)

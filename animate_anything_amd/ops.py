@@ -17,7 +17,7 @@ import torch
 
 from . import _lib
 from ._lib import (AA_ACT_GELU, AA_ACT_NONE, AA_ACT_QUICK_GELU, AA_ACT_SILU, AA_BF16, AA_F16, AA_F32, AaAttention, AaAttnOperand,
-                   AaBlend, AaConvGemm, AaFFFused, AaLinearRows, AaLinearFp8, AaQuantRowsFp8, AaDdimStepTok, AaDpmStep, AaDpmStepTok, AaEulerStepTok, AaGroupNorm, AaPackFrames, AaPackLatents, AaSeqSelfAttn, AaUnipcStepTok, AaFreeU, AaCfgRescale)
+                   AaBlend, AaConvGemm, AaFFFused, AaLinearRows, AaLinearFp8, AaQuantRowsFp8, AaDdimStepTok, AaDpmStep, AaDpmStepTok, AaEulerStepTok, AaGroupNorm, AaPackFrames, AaPackLatents, AaSeqSelfAttn, AaUnipcStepTok, AaFreeU, AaCfgRescale, AaWindow, AaWindowGather, AaWindowMerge)
 
 _DT = {torch.float16: AA_F16, torch.bfloat16: AA_BF16, torch.float32: AA_F32}
 
@@ -1432,3 +1432,76 @@ def cfg_rescale_tokens(tokens: torch.Tensor, clips: int, channels: int, frames: 
         ws = _CFG_RESCALE_WS[key] = torch.empty(max(nbytes // 8, 1), dtype=torch.float64, device=tokens.device)
     _run(lib.aa_cfg_rescale_tokens, C.byref(d), _ptr(ws), ws.numel() * 8, _stream(tokens))
     return out
+
+
+# ------------------------------------------------------------------------------------- context windows
+def window_desc(window) -> AaWindow:
+    """One window of schedulers.context_windows - (frame_indices, normalised_weights, first_flags, last_flags) - as the by-value
+    block both window descriptors carry.  An AaWindow passes through.  The slot count is left to the entry points to judge (one past
+    AA_WINDOW_MAX is recorded as such and refused there)."""
+    if isinstance(window, AaWindow):
+        return window
+    frames, weights, first, last = window
+    n = len(frames)
+    if not (len(weights) == len(first) == len(last) == n):
+        raise RuntimeError("window_desc: frame indices, weights and flags differ in length")
+    w = AaWindow()
+    w.window_frames = n
+    for j in range(min(n, _lib.AA_WINDOW_MAX)):
+        w.frame[j], w.weight[j], w.first[j], w.last[j] = int(frames[j]), float(weights[j]), int(bool(first[j])), int(bool(last[j]))
+    return w
+
+
+def window_gather_latents(src: torch.Tensor, window, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out[b, c, j] = src[b, c, frame[j]] on fp32 latents [clips, C, frames, h, w] (aa_window_gather_latents, bit-exact): the window's
+    frames into `out` [clips, C, window_frames, h, w] - the UNet session's `sample` input; None: a new tensor.  Returns `out`."""
+    lib = _lib.get()
+    w = window_desc(window)
+    if src.dim() != 5 or src.dtype != torch.float32:
+        raise RuntimeError("window_gather_latents: src must be fp32 [clips, C, frames, h, w]")
+    clips, c, frames, h, wd = src.shape
+    if out is None:
+        out = torch.empty((clips, c, max(w.window_frames, 0), h, wd), dtype=torch.float32, device=src.device)
+    _check(src, out)
+    if out.dtype != torch.float32 or tuple(out.shape) != (clips, c, w.window_frames, h, wd) or out.device != src.device:
+        raise RuntimeError(f"window_gather_latents: out must be fp32 {(clips, c, w.window_frames, h, wd)} on the source's device")
+    d = AaWindowGather()
+    d.src, d.dst = _ptr(src), _ptr(out)
+    d.clips, d.channels, d.total_frames, d.hw = clips, c, frames, h * wd
+    d.window = w
+    _run(lib.aa_window_gather_latents, C.byref(d), _stream(src))
+    return out
+
+
+def window_merge_tokens(tokens: torch.Tensor, acc: torch.Tensor, merged: torch.Tensor, window, guidance) -> torch.Tensor:
+    """One window's share of a context-window step (aa_window_merge_tokens; one call per window, in schedule order): the guided
+    prediction of the window - `tokens` [(2*)clips*(window_frames+1)*hw, >= C], the UNet's token-layout output read as the step
+    kernels read it, `guidance` None = off - times the slot's weight into `acc` (fp32 [clips, frames, hw, C]: written by a frame's
+    first window, added to after), and by a frame's last window rounded into `merged` [(2*)clips*(frames+1)*hw, >= C] (the tokens'
+    dtype; both halves under guidance), which the step kernel then reads with the SAME guidance: a frame held by one window is copied
+    bit for bit, u and t alike, without touching `acc`; a blended frame's value goes to both halves, where guidance leaves it as it is.
+    Rows may be pitched (stride(0) >= C, stride(1) == 1).  Returns `merged`."""
+    lib = _lib.get()
+    w = window_desc(window)
+    if acc.dim() != 4 or acc.dtype != torch.float32:
+        raise RuntimeError("window_merge_tokens: acc must be fp32 [clips, frames, hw, C]")
+    _check(acc)
+    clips, frames, hw, c = acc.shape
+    halves = 2 if guidance is not None else 1
+    for name, t, need in (("tokens", tokens, halves * clips * (w.window_frames + 1) * hw), ("merged", merged, halves * clips * (frames + 1) * hw)):
+        if not t.is_cuda and not _lib.host_pointers_ok():
+            raise RuntimeError("animate_anything_amd ops run on the GPU only (tensor is on %s)" % t.device)
+        if t.dim() != 2 or (t.shape[1] > 1 and t.stride(1) != 1) or t.dtype != tokens.dtype or t.dtype not in (torch.float16, torch.bfloat16):
+            raise RuntimeError(f"window_merge_tokens: {name} must be a 2-d fp16 / bf16 token matrix with contiguous rows, both of one dtype")
+        if t.device != acc.device:
+            raise RuntimeError(f"window_merge_tokens: {name} is on {t.device}, acc on {acc.device}")
+        if t.shape[0] < need or t.shape[1] < c:
+            raise RuntimeError(f"window_merge_tokens: {name} {tuple(t.shape)} does not hold {need} rows of {c} channels")
+    d = AaWindowMerge()
+    d.tokens, d.acc, d.merged = _ptr(tokens), _ptr(acc), _ptr(merged)
+    d.clips, d.channels, d.total_frames, d.hw = clips, c, frames, hw
+    d.ld, d.out_ld = tokens.stride(0), merged.stride(0)
+    d.guidance_on, d.guidance, d.dtype = int(guidance is not None), float(guidance or 0.0), _DT[tokens.dtype]
+    d.window = w
+    _run(lib.aa_window_merge_tokens, C.byref(d), _stream(acc))
+    return merged

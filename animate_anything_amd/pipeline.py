@@ -18,7 +18,7 @@ import numpy as np
 import torch
 
 from . import ops
-from .schedulers import DDIMScheduler, DPMSolverMultistepScheduler, UniPCMultistepScheduler
+from .schedulers import CONTEXT_WEIGHTS, DDIMScheduler, DPMSolverMultistepScheduler, UniPCMultistepScheduler, context_windows
 
 
 class TextToVideoSDPipelineOutput(SimpleNamespace):
@@ -98,6 +98,47 @@ def _check_guidance_rescale(guidance_rescale):
     if not 0.0 <= r <= 1.0:                                   # (NaN fails both comparisons)
         raise ValueError(f"guidance_rescale {guidance_rescale!r}: a number in [0, 1]")
     return r
+
+
+CONTEXT_DEFAULTS = dict(frames=16, overlap=4, weights="pyramid", closed_loop=False)
+CONTEXT_MAX_FRAMES = 64                                       # AA_WINDOW_MAX: the slots a window descriptor carries by value
+
+
+def check_context(context):
+    """The `context` argument (context windows: sampling clips longer than the UNet's frame window): None (off), or a mapping with the
+    keys of CONTEXT_DEFAULTS - `frames` (window length, 1 .. 64), `overlap` (0 <= overlap < frames), `weights` ("flat" / "pyramid"),
+    `closed_loop` - any of them left out taking its default; an unknown key or a value out of range raises ValueError.  Returns the
+    completed dict, or None."""
+    if context is None:
+        return None
+    if not hasattr(context, "keys"):
+        raise ValueError(f"context {context!r}: a mapping with keys from {sorted(CONTEXT_DEFAULTS)}")
+    unknown = sorted(set(context.keys()) - set(CONTEXT_DEFAULTS))
+    if unknown:
+        raise ValueError(f"context: unknown key(s) {unknown} (known: {sorted(CONTEXT_DEFAULTS)})")
+    c = dict(CONTEXT_DEFAULTS)
+    c.update({k: context[k] for k in context.keys()})
+    for k in ("frames", "overlap"):
+        if isinstance(c[k], bool) or not isinstance(c[k], int):
+            raise ValueError(f"context.{k} = {c[k]!r}: an integer")
+    if not 1 <= c["frames"] <= CONTEXT_MAX_FRAMES:
+        raise ValueError(f"context.frames = {c['frames']}: a window of 1 .. {CONTEXT_MAX_FRAMES} frames")
+    if not 0 <= c["overlap"] < c["frames"]:
+        raise ValueError(f"context.overlap = {c['overlap']}: 0 <= overlap < frames ({c['frames']})")
+    if c["weights"] not in CONTEXT_WEIGHTS:
+        raise ValueError(f"context.weights = {c['weights']!r}: one of {CONTEXT_WEIGHTS}")
+    if not isinstance(c["closed_loop"], bool):
+        raise ValueError(f"context.closed_loop = {c['closed_loop']!r}: true or false")
+    return c
+
+
+def _context_schedule(context, num_frames):
+    """The step's windows (schedulers.context_windows) when `context` asks for a window shorter than the clip, else None: the
+    unwindowed loop."""
+    c = check_context(context)
+    if c is None or c["frames"] >= num_frames:
+        return None
+    return context_windows(num_frames, c["frames"], c["overlap"], c["closed_loop"], c["weights"])
 
 
 def tensor2vid(video):
@@ -222,7 +263,7 @@ class LatentToVideoPipeline:
 
     # ------------------------------------------------------------------ denoising
     def denoise(self, latents, prompt_embeds, condition_latent, mask, motion, timesteps, guidance_scale,
-                callback=None, callback_steps=1, eta=0.0, generator=None, guidance_rescale=0.0):
+                callback=None, callback_steps=1, eta=0.0, generator=None, guidance_rescale=0.0, context=None):
         """The hot loop (reference pipeline.py:163-198).  `prompt_embeds` already holds [uncond; text]
         when guidance is on.  Latents are kept in fp32.
 
@@ -235,16 +276,24 @@ class LatentToVideoPipeline:
         the length of the call (the corrected sample and three data predictions).
         `guidance_rescale` > 0 under guidance (diffusers' argument, `rescale_noise_cfg`): the step becomes session run,
         ops.cfg_rescale_tokens - the rescaled guided prediction written over the unconditional half of the token matrix, two
-        launches - and the same solver kernel with guidance off.  With 0, the default, a step issues what it issued before."""
+        launches - and the same solver kernel with guidance off.  With 0, the default, a step issues what it issued before.
+        `context` (check_context; context windows) with `frames` below the clip's length: the session is built for `frames` frames and
+        the fp32 latents of the whole clip live in a buffer of their own; per step every window of schedulers.context_windows runs
+        ops.window_gather_latents into the session's `sample`, the session, (ops.cfg_rescale_tokens, per window,) and
+        ops.window_merge_tokens, which blends the window's prediction into one token matrix of the clip's length (both guidance halves:
+        a frame held by one window keeps the UNet's bits); then the same solver kernel runs once on that matrix with the same guidance.  The solver state is sized from the long latents.  None, or a window
+        that holds the whole clip: the loop of before, no window op."""
         cfg = guidance_scale > 1.0
         rescale = _check_guidance_rescale(guidance_rescale) if cfg else 0.0
+        windows = _context_schedule(context, latents.shape[2])
         sched = self.scheduler
         unet = self.unet
         if not (isinstance(sched, (DPMSolverMultistepScheduler, DDIMScheduler, UniPCMultistepScheduler)) and hasattr(unet, "session")):
             return self._denoise_generic(latents, prompt_embeds, condition_latent, mask, motion, timesteps, guidance_scale,
-                                         callback, callback_steps, eta, generator, guidance_rescale=guidance_rescale)
+                                         callback, callback_steps, eta, generator, guidance_rescale=guidance_rescale, context=context)
         dev = latents.device
         b0, _, frames, h, w = latents.shape
+        wf = frames if windows is None else len(windows[0][0])  # frames the UNet sees at a time
         use_mask = bool(unet.motion_mask and mask is not None)
         has_motion = bool(unet.motion_strength and motion is not None)
         pair = self.guidance_group if cfg else None
@@ -261,7 +310,7 @@ class LatentToVideoPipeline:
             # differ only in the text: the UNet computes the text-independent prefix once (UNet3DConditionModel._core cfg_dup)
             b, text = 2 * b0 if cfg else b0, prompt_embeds
             shared = cfg and self.cfg_shared_prefix and b0 % condition_latent.shape[0] == 0 and (not use_mask or b0 % mask.shape[0] == 0)
-        sess = unet.session(b, frames, h, w, tuple(text.shape[1:]), use_mask, has_motion, False, torch.float32, b0,
+        sess = unet.session(b, wf, h, w, tuple(text.shape[1:]), use_mask, has_motion, False, torch.float32, b0,
                             condition_latent.shape[0], mask.shape[0] if use_mask else 0, dev, cfg_dup=shared)
         tokens = sess.run                                       # [b*(T+1)*h*w, 8], columns [0, out_channels) valid (row pitch = stride(0))
         if pair is not None:
@@ -271,15 +320,32 @@ class LatentToVideoPipeline:
         if has_motion:
             mot = torch.as_tensor(motion, device=dev).to(torch.float32).reshape(-1).expand(b).contiguous()
         ts = [int(t) for t in timesteps]
-        sess.load(sample=latents, cond=condition_latent, mask=mask if use_mask else None, text=text, motion=mot,
+        sess.load(sample=latents if windows is None else None, cond=condition_latent, mask=mask if use_mask else None, text=text, motion=mot,
                   t=torch.full((b,), float(ts[0]) if ts else 0.0, dtype=torch.float32, device=dev))
-        x = sess.inputs["sample"]                               # fp32 [b0,C,T,h,w]: updated in place by the solver kernel
-        step = self._solver_step(x, eta, generator)
         guidance = guidance_scale if cfg else None
+        if windows is None:
+            x = sess.inputs["sample"]                           # fp32 [b0,C,T,h,w]: updated in place by the solver kernel
+        else:
+            # the clip's latents in a buffer of their own; the session's `sample` holds one window at a time (the gather fills it)
+            x = latents.to(torch.float32).contiguous().clone()
+            descs = [ops.window_desc(win) for win in windows]
+            acc = torch.empty((b0, frames, h * w, x.shape[1]), dtype=torch.float32, device=dev)
+            halves = 2 if cfg and rescale == 0.0 else 1         # a UNet output of the clip's length: [uncond clips | text clips]
+            merged = torch.zeros((halves * b0 * (frames + 1) * h * w, 8), dtype=unet.dtype, device=dev)
+        step = self._solver_step(x, eta, generator)
         for i, t in enumerate(ts):
-            tok = tokens()
-            if rescale > 0.0:                                   # in place: the next session run (or gather) rewrites the matrix
-                ops.cfg_rescale_tokens(tok, b0, x.shape[1], frames, h * w, guidance_scale, rescale)
+            if windows is None:
+                tok = tokens()
+                if rescale > 0.0:                               # in place: the next session run (or gather) rewrites the matrix
+                    ops.cfg_rescale_tokens(tok, b0, x.shape[1], frames, h * w, guidance_scale, rescale)
+            else:
+                for win in descs:                               # schedule order: a frame's first window writes `acc`, its last `merged`
+                    ops.window_gather_latents(x, win, out=sess.inputs["sample"])
+                    wtok = tokens()
+                    if rescale > 0.0:                           # per window (a departure: the deviations are the window's, not the clip's)
+                        ops.cfg_rescale_tokens(wtok, b0, x.shape[1], wf, h * w, guidance_scale, rescale)
+                    ops.window_merge_tokens(wtok, acc, merged, win, None if rescale > 0.0 else guidance)
+                tok = merged
             step(tok, None if rescale > 0.0 else guidance, t, i, sess.inputs["t"], float(ts[i + 1]) if i + 1 < len(ts) else float(t))
             if callback is not None and i % callback_steps == 0:
                 callback(i, t, x)
@@ -320,15 +386,18 @@ class LatentToVideoPipeline:
         return [torch.zeros_like(x) for _ in range(4)]
 
     def _denoise_generic(self, latents, prompt_embeds, condition_latent, mask, motion, timesteps, guidance_scale,
-                         callback=None, callback_steps=1, eta=0.0, generator=None, guidance_rescale=0.0):
+                         callback=None, callback_steps=1, eta=0.0, generator=None, guidance_rescale=0.0, context=None):
         """Any scheduler with a diffusers-style `step()`: the UNet through its module `forward`, guidance and the update as
         torch expressions (the reference's own sequence, pipeline.py:165-192).  `eta` / `generator` go to a `step()` that
         names them (diffusers' prepare_extra_step_kwargs, pipeline.py:156); DDIM's variance noise is drawn here exactly as
         the fused loop draws it, so both consume the generator alike.  `guidance_rescale` > 0 under guidance applies
-        `rescale_noise_cfg` to the guided prediction."""
+        `rescale_noise_cfg` to the guided prediction.  `context` with a window shorter than the clip (check_context): per step the
+        module forward, guidance and `rescale_noise_cfg` run per window of schedulers.context_windows, the guided predictions are
+        summed in fp32 with the windows' per-frame weights, and `step()` is applied once to the whole clip."""
         import inspect
         cfg = guidance_scale > 1.0
         rescale = _check_guidance_rescale(guidance_rescale) if cfg else 0.0
+        windows = _context_schedule(context, latents.shape[2])
         dt = self.unet.dtype
         sched = self.scheduler
         accepted = set(inspect.signature(sched.step).parameters)
@@ -339,15 +408,28 @@ class LatentToVideoPipeline:
             extra["generator"] = generator
         x = latents.float().contiguous()
         cond = torch.cat([condition_latent, condition_latent]) if cfg else condition_latent     # :160-161
-        for i, t in enumerate(timesteps):
-            x_lp = x.to(dt)
+
+        def predict(xs, t):
+            """The (guided, rescaled) fp32 prediction for the latents `xs` - the clip, or one window of it."""
+            x_lp = xs.to(dt)
             model_in = torch.cat([x_lp, x_lp]) if cfg else x_lp                                  # :165
             eps = self.unet(model_in, t, encoder_hidden_states=prompt_embeds, condition_latent=cond, mask=mask,
                             motion=None if motion is None else torch.as_tensor(motion, device=x.device)).sample
-            e_u, e_t = (eps[: x.shape[0]], eps[x.shape[0]:]) if cfg else (eps, eps)
+            e_u, e_t = (eps[: xs.shape[0]], eps[xs.shape[0]:]) if cfg else (eps, eps)
             e = e_u.float() + guidance_scale * (e_t.float() - e_u.float()) if cfg else eps.float()
             if rescale > 0.0:
                 e = rescale_noise_cfg(e, e_t.float(), rescale)
+            return e
+
+        for i, t in enumerate(timesteps):
+            if windows is None:
+                e = predict(x, t)
+            else:
+                e = torch.zeros_like(x)
+                for idx, wn, _first, _last in windows:
+                    idx = torch.as_tensor(idx, device=x.device)
+                    wn = torch.tensor(wn, dtype=torch.float64).to(device=x.device, dtype=torch.float32).reshape(1, 1, -1, 1, 1)
+                    e[:, :, idx] += wn * predict(x[:, :, idx], t)
             b, c, f, h, w = x.shape
             if isinstance(sched, DDIMScheduler) and eta > 0:
                 extra["variance_noise"] = _variance_noise(x, generator)
@@ -363,7 +445,7 @@ class LatentToVideoPipeline:
                  guidance_scale=9.0, negative_prompt=None, eta=0.0, generator=None, latents=None,
                  prompt_embeds=None, negative_prompt_embeds=None, output_type="np", return_dict=True,
                  callback=None, callback_steps=1, cross_attention_kwargs=None, condition_latent=None,
-                 mask=None, timesteps=None, motion=None, guidance_rescale=0.0):
+                 mask=None, timesteps=None, motion=None, guidance_rescale=0.0, context=None):
         if latents is None:
             raise ValueError("LatentToVideoPipeline expects caller-prepared `latents` (reference pipeline.py:153)")
         height = height or latents.shape[-2] * self.vae_scale_factor
@@ -376,7 +458,8 @@ class LatentToVideoPipeline:
         if timesteps is None:
             timesteps = self.scheduler.timesteps
         x = self.denoise(latents, prompt_embeds, condition_latent, mask, motion, [int(t) for t in timesteps],
-                         guidance_scale, callback, callback_steps, eta=eta, generator=generator, guidance_rescale=guidance_rescale)
+                         guidance_scale, callback, callback_steps, eta=eta, generator=generator, guidance_rescale=guidance_rescale,
+                         context=context)
         latents = x.to(self.unet.dtype)
         if self.vae is None or output_type == "latent":
             video = None

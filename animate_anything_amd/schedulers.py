@@ -518,3 +518,50 @@ class EulerDiscreteScheduler(_Scheduler):
         prev = (x + (x - x0) / s * (sn - s)).to(sample.dtype)
         self._step_index += 1
         return SchedulerOutput(prev_sample=prev, pred_original_sample=x0.to(sample.dtype)) if return_dict else (prev,)
+
+
+# ------------------------------------------------------------------------------------- context windows
+CONTEXT_WEIGHTS = ("flat", "pyramid")
+
+
+def context_windows(num_frames, length, overlap, closed_loop=False, weights="pyramid"):
+    """The window schedule of one denoising step over a clip of `num_frames` frames for a UNet that sees `length` frames at a time
+    (MultiDiffusion over time, the context windows of the AnimateDiff ecosystem): a list of windows
+    (frame_indices, normalised_weights, first_flags, last_flags), one entry per slot each.
+
+    num_frames <= length: the single window range(num_frames) (callers treat it as "feature off").  Open clip, stride s = length -
+    overlap: starts 0, s, 2s, ... while start + length < num_frames, then num_frames - length unless already present; window =
+    range(start, start + length).  `closed_loop` (looping clips): starts 0, s, ... < num_frames, indices (start + j) % num_frames.
+    Raw slot weights: "flat" 1, "pyramid" min(j + 1, length - j).  Normalisation per frame in float64: w_j over the sum of the raw
+    weights of every (window, slot) that holds the frame - a frame held once gets exactly 1.0.  first[k][j] / last[k][j]: no earlier /
+    no later window in list order holds the frame."""
+    num_frames, length, overlap = int(num_frames), int(length), int(overlap)
+    if length < 1 or not 0 <= overlap < length or num_frames < 1:
+        raise ValueError(f"context_windows: need 1 <= length, 0 <= overlap < length and num_frames >= 1 (got num_frames {num_frames}, "
+                         f"length {length}, overlap {overlap})")
+    if weights not in CONTEXT_WEIGHTS:
+        raise ValueError(f"context_windows: weights {weights!r} is not one of {CONTEXT_WEIGHTS}")
+    if num_frames <= length:
+        n = num_frames
+        return [(list(range(n)), [1.0] * n, [True] * n, [True] * n)]
+    stride = length - overlap
+    if closed_loop:
+        frames = [[(start + j) % num_frames for j in range(length)] for start in range(0, num_frames, stride)]
+    else:
+        starts = []
+        start = 0
+        while start + length < num_frames:
+            starts.append(start)
+            start += stride
+        if num_frames - length not in starts:
+            starts.append(num_frames - length)
+        frames = [list(range(start, start + length)) for start in starts]
+    raw = [1.0 if weights == "flat" else float(min(j + 1, length - j)) for j in range(length)]
+    total = np.zeros(num_frames, dtype=np.float64)
+    holders = [[] for _ in range(num_frames)]                   # windows that hold the frame, in list order
+    for k, idx in enumerate(frames):
+        for j, f in enumerate(idx):
+            total[f] += raw[j]
+            holders[f].append(k)
+    return [(idx, [float(np.float64(raw[j]) / total[f]) for j, f in enumerate(idx)],
+             [holders[f][0] == k for f in idx], [holders[f][-1] == k for f in idx]) for k, idx in enumerate(frames)]

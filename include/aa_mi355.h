@@ -715,6 +715,65 @@ typedef struct AaCfgRescale {
 size_t aa_cfg_rescale_workspace(const AaCfgRescale* d);
 int aa_cfg_rescale_tokens(const AaCfgRescale* d, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Context windows (MultiDiffusion over time; the AnimateDiff ecosystem's remedy for clips longer than the UNet's trained frame window; not
+ * in the reference): per step the UNet runs on overlapping windows of `window_frames` of the clip's `total_frames` latent frames, the
+ * per-window predictions are blended per frame and ONE solver update is applied to the whole clip.  Both entry points carry the window by
+ * value: slot j of the window holds frame `frame[j]` of the clip with the per-frame normalised weight `weight[j]`; `first[j]` / `last[j]`
+ * say that no earlier / no later window of the step's schedule holds that frame (schedulers.context_windows).
+ *
+ * aa_window_gather_latents: dst[b, c, j, p] = src[b, c, frame[j], p] on fp32 latents (bit-exact); dst is the UNet session's `sample`
+ * input.  `weight`, `first` and `last` are not read.
+ *
+ * aa_window_merge_tokens: one launch per window, in schedule order, after that window's UNet run.  Reads the UNet's token matrix
+ * [(2 *) clips * (window_frames + 1) * hw][ld] as the step kernels do (frame 0 skipped, unconditional clips first, u + guidance * (t - u)
+ * in fp32 under guidance, u alone without) and, for slot j with v = weight[j] * guided:
+ *   first && last    merged = the window's tokens       (the accumulator is not touched; the input's bits, BOTH halves under guidance)
+ *   first && !last   acc = v                            (written, not added: the accumulator never needs zeroing)
+ *   !first && !last  acc += v
+ *   !first && last   merged = (T)(acc + v)              (the accumulator is not written; under guidance the value goes to both halves)
+ * `acc` is fp32 [clips][total_frames][hw][channels] (token-major), `merged` is [(guidance_on ? 2 : 1) * clips * (total_frames + 1) * hw]
+ * [out_ld] in the storage type, laid out like a UNet output of total_frames frames, unconditional clips first: its frame-0 rows and its
+ * columns >= channels are never written.  The step kernels then consume `merged` with clips, frames = total_frames and THE SAME guidance:
+ * a frame held by one window reaches them as the u and t the unwindowed step would read (u + g (t - u) formed once, in fp32, by the
+ * step kernel - overlap-0 windows equal plain runs of the parts bit for bit); a blended frame holds its value c in both halves, and
+ * c + g (c - c) is c exactly.  No atomics: a launch touches each (clip, frame, pixel) once and the stream orders the launches, so a
+ * replay or a second run repeats the bits.
+ * Refused with nothing launched - AA_E_SHAPE: a null descriptor or pointer; a size below 1; more than 8 channels (merge); more than 65535
+ * clips (gather: clips * channels); 2^31 or more token rows or latent elements; window_frames > AA_WINDOW_MAX or > total_frames; a frame
+ * index outside [0, total_frames) or repeated inside the window; a pitch below channels; a weight or guidance that is not finite; any
+ * overlap among tokens, acc and merged (src and dst).  AA_E_ALIGN: tokens / merged not 2-byte, acc / src / dst not 4-byte aligned (wider
+ * alignment only selects the 8- / 16-byte form of the kernels).  AA_E_DTYPE (merge): a dtype other than AA_F16 / AA_BF16. */
+#define AA_WINDOW_MAX 64
+typedef struct AaWindow {
+    int32_t window_frames;            /* slots in use: 1 .. AA_WINDOW_MAX */
+    int32_t frame[AA_WINDOW_MAX];     /* frame of the clip held by slot j, distinct inside the window */
+    float weight[AA_WINDOW_MAX];      /* w_j / sum of the raw weights of every (window, slot) that holds the frame */
+    int32_t first[AA_WINDOW_MAX];     /* 1: no earlier window holds the frame */
+    int32_t last[AA_WINDOW_MAX];      /* 1: no later window holds the frame */
+} AaWindow;
+
+typedef struct AaWindowGather {
+    const float* src;         /* fp32 [clips][channels][total_frames][hw] */
+    float* dst;               /* fp32 [clips][channels][window_frames][hw] */
+    int32_t clips, channels, total_frames, hw;
+    AaWindow window;
+} AaWindowGather;
+
+typedef struct AaWindowMerge {
+    const void* tokens;       /* [(guidance_on ? 2 : 1) * clips * (window_frames + 1) * hw][ld] */
+    float* acc;               /* fp32 [clips][total_frames][hw][channels] */
+    void* merged;             /* [(guidance_on ? 2 : 1) * clips * (total_frames + 1) * hw][out_ld] */
+    int32_t clips, channels, total_frames, hw;
+    int32_t ld, out_ld;       /* row pitches in elements (>= channels; 4 is legal) */
+    int32_t guidance_on;
+    float guidance;
+    int32_t dtype;            /* AA_F16 / AA_BF16 */
+    AaWindow window;
+} AaWindowMerge;
+
+int aa_window_gather_latents(const AaWindowGather* d, void* stream);
+int aa_window_merge_tokens(const AaWindowMerge* d, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
