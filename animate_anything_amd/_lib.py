@@ -219,11 +219,63 @@ class AaWindowMerge(C.Structure):
     ]
 
 
-SYMBOLS = ("aa_version", "aa_last_error", "aa_set_tile_override", "aa_conv_gemm_tile_info", "aa_conv_gemm_tile_ok", "aa_conv_gemm_workspace", "aa_conv_gemm", "aa_conv_gemm_launch_count", "aa_conv_gemm_row_stats_parts", "aa_conv_gemm_row_coef_ok", "aa_conv_gemm_tickets", "aa_conv_gemm_reduce_launches", "aa_conv_gemm_tile_flags", "aa_ln_finalize", "aa_groupnorm_workspace", "aa_groupnorm", "aa_groupnorm_coef", "aa_set_groupnorm_two_pass", "aa_groupnorm_plan",
-           "aa_layernorm", "aa_attention", "aa_seq_self_attention_ok", "aa_seq_self_attention", "aa_ff_fused_ok", "aa_ff_fused", "aa_linear_rows_ok", "aa_linear_rows", "aa_quant_rows_fp8", "aa_linear_fp8", "aa_softmax_rows", "aa_cfg_dpm_step",
-           "aa_timestep_embedding", "aa_pack_latents", "aa_cfg_dpm_step_tokens",
-           "aa_blend", "aa_pack_frames", "aa_cfg_euler_step_tokens", "aa_cfg_ddim_step_tokens", "aa_cfg_unipc_step_tokens", "aa_freeu_tokens",
-           "aa_cfg_rescale_workspace", "aa_cfg_rescale_tokens", "aa_window_gather_latents", "aa_window_merge_tokens")
+_I, _I32, _I64, _F, _V, _Z, _P = C.c_int, C.c_int32, C.c_int64, C.c_float, C.c_void_p, C.c_size_t, C.POINTER
+
+
+def _launch(desc):
+    """int f(const Desc* d, void* stream)"""
+    return _I, [_P(desc), _V]
+
+
+# The C ABI, in the order of include/aa_mi355.h: name -> (restype, argtypes).  A new entry point is one row here
+# (tests/test_abi.py holds the rows and the structures above against the header).
+PROTOTYPES = {
+    "aa_version": (_I, []),
+    "aa_last_error": (C.c_char_p, []),
+    "aa_conv_gemm_workspace": (_Z, [_P(AaConvGemm)]),
+    "aa_conv_gemm": _launch(AaConvGemm),
+    "aa_conv_gemm_launch_count": (_I, [_P(AaConvGemm)]),
+    "aa_conv_gemm_tickets": (_I, [_P(AaConvGemm)]),
+    "aa_conv_gemm_reduce_launches": (_I, [_P(AaConvGemm)]),
+    "aa_conv_gemm_row_stats_parts": (_I, [_P(AaConvGemm)]),
+    "aa_conv_gemm_row_coef_ok": (_I, [_P(AaConvGemm)]),
+    "aa_ln_finalize": (_I, [_V, _I32, _V, _I64, _I32, _F, _V]),
+    "aa_conv_gemm_tile_info": (_I, [_I, _P(_I32)]),
+    "aa_conv_gemm_tile_flags": (_I, [_I]),
+    "aa_conv_gemm_tile_ok": (_I, [_P(AaConvGemm), _I]),
+    "aa_set_tile_override": (None, [_I]),
+    "aa_groupnorm_workspace": (_Z, [_P(AaGroupNorm)]),
+    "aa_set_groupnorm_two_pass": (None, [_I]),
+    "aa_groupnorm_plan": (_I, [_P(AaGroupNorm), _P(_I32)]),
+    "aa_groupnorm": (_I, [_P(AaGroupNorm), _V, _Z, _V]),
+    "aa_groupnorm_coef": (_I, [_P(AaGroupNorm), _V, _Z, _V, _V]),
+    "aa_layernorm": (_I, [_V, _V, _V, _V, _I64, _I32, _F, _I32, _V]),
+    "aa_attention": _launch(AaAttention),
+    "aa_seq_self_attention_ok": (_I, [_P(AaSeqSelfAttn)]),
+    "aa_seq_self_attention": _launch(AaSeqSelfAttn),
+    "aa_ff_fused_ok": (_I, [_P(AaFFFused)]),
+    "aa_ff_fused": _launch(AaFFFused),
+    "aa_linear_rows_ok": (_I, [_P(AaLinearRows)]),
+    "aa_linear_rows": _launch(AaLinearRows),
+    "aa_quant_rows_fp8": _launch(AaQuantRowsFp8),
+    "aa_linear_fp8": _launch(AaLinearFp8),
+    "aa_softmax_rows": (_I, [_V, _V, _I64, _I32, _I32, _I32, _I32, _V]),
+    "aa_cfg_dpm_step": _launch(AaDpmStep),
+    "aa_timestep_embedding": (_I, [_V, _V, _I32, _I32, _I32, _V]),
+    "aa_pack_latents": _launch(AaPackLatents),
+    "aa_cfg_dpm_step_tokens": _launch(AaDpmStepTok),
+    "aa_blend": _launch(AaBlend),
+    "aa_pack_frames": _launch(AaPackFrames),
+    "aa_cfg_euler_step_tokens": _launch(AaEulerStepTok),
+    "aa_cfg_ddim_step_tokens": _launch(AaDdimStepTok),
+    "aa_cfg_unipc_step_tokens": _launch(AaUnipcStepTok),
+    "aa_freeu_tokens": _launch(AaFreeU),
+    "aa_cfg_rescale_workspace": (_Z, [_P(AaCfgRescale)]),
+    "aa_cfg_rescale_tokens": (_I, [_P(AaCfgRescale), _V, _Z, _V]),
+    "aa_window_gather_latents": _launch(AaWindowGather),
+    "aa_window_merge_tokens": _launch(AaWindowMerge),
+}
+SYMBOLS = tuple(PROTOTYPES)
 
 DEFAULT_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libaa_mi355.so")
 
@@ -234,68 +286,11 @@ def bind(path: str) -> C.CDLL:
         raise RuntimeError(f"{path} is missing: build it with `python -m animate_anything_amd.build` "
                            "(hipcc --offload-arch=gfx950); this package has no fallback backend")
     lib = C.CDLL(path)
-    for s in SYMBOLS:
-        if not hasattr(lib, s):
-            raise RuntimeError(f"{path} does not export {s}")
-    lib.aa_version.restype = C.c_int
-    lib.aa_last_error.restype = C.c_char_p
-    lib.aa_set_tile_override.argtypes = [C.c_int]
-    lib.aa_set_tile_override.restype = None
-    lib.aa_conv_gemm_tile_info.argtypes = [C.c_int, C.POINTER(C.c_int32)]
-    lib.aa_conv_gemm_tile_info.restype = C.c_int
-    lib.aa_conv_gemm_tile_ok.argtypes = [C.POINTER(AaConvGemm), C.c_int]
-    lib.aa_conv_gemm_tile_ok.restype = C.c_int
-    lib.aa_conv_gemm.argtypes = [C.POINTER(AaConvGemm), C.c_void_p]
-    lib.aa_ln_finalize.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_float, C.c_void_p]
-    lib.aa_ln_finalize.restype = C.c_int
-    lib.aa_conv_gemm_row_stats_parts.argtypes = [C.POINTER(AaConvGemm)]
-    lib.aa_conv_gemm_row_stats_parts.restype = C.c_int
-    lib.aa_conv_gemm_row_coef_ok.argtypes = [C.POINTER(AaConvGemm)]
-    lib.aa_conv_gemm_row_coef_ok.restype = C.c_int
-    lib.aa_conv_gemm_launch_count.argtypes = [C.POINTER(AaConvGemm)]
-    lib.aa_conv_gemm_tickets.argtypes = [C.POINTER(AaConvGemm)]
-    lib.aa_conv_gemm_reduce_launches.argtypes = [C.POINTER(AaConvGemm)]
-    lib.aa_conv_gemm_tile_flags.argtypes = [C.c_int]
-    lib.aa_set_groupnorm_two_pass.argtypes = [C.c_int]
-    lib.aa_set_groupnorm_two_pass.restype = None
-    lib.aa_groupnorm_plan.argtypes = [C.POINTER(AaGroupNorm), C.POINTER(C.c_int32)]
-    lib.aa_groupnorm_plan.restype = C.c_int
-    lib.aa_conv_gemm_workspace.argtypes = [C.POINTER(AaConvGemm)]
-    lib.aa_conv_gemm_workspace.restype = C.c_size_t
-    lib.aa_groupnorm_workspace.argtypes = [C.POINTER(AaGroupNorm)]
-    lib.aa_groupnorm_workspace.restype = C.c_size_t
-    lib.aa_groupnorm.argtypes = [C.POINTER(AaGroupNorm), C.c_void_p, C.c_size_t, C.c_void_p]
-    lib.aa_layernorm.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32,
-                                 C.c_float, C.c_int32, C.c_void_p]
-    lib.aa_attention.argtypes = [C.POINTER(AaAttention), C.c_void_p]
-    lib.aa_seq_self_attention_ok.argtypes = [C.POINTER(AaSeqSelfAttn)]
-    lib.aa_seq_self_attention.argtypes = [C.POINTER(AaSeqSelfAttn), C.c_void_p]
-    lib.aa_ff_fused_ok.argtypes = [C.POINTER(AaFFFused)]
-    lib.aa_ff_fused.argtypes = [C.POINTER(AaFFFused), C.c_void_p]
-    lib.aa_groupnorm_coef.argtypes = [C.POINTER(AaGroupNorm), C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
-    lib.aa_linear_rows_ok.argtypes = [C.POINTER(AaLinearRows)]
-    lib.aa_linear_rows.argtypes = [C.POINTER(AaLinearRows), C.c_void_p]
-    lib.aa_quant_rows_fp8.argtypes = [C.POINTER(AaQuantRowsFp8), C.c_void_p]
-    lib.aa_linear_fp8.argtypes = [C.POINTER(AaLinearFp8), C.c_void_p]
-    lib.aa_softmax_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]
-    lib.aa_cfg_dpm_step.argtypes = [C.POINTER(AaDpmStep), C.c_void_p]
-    lib.aa_timestep_embedding.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]
-    lib.aa_pack_latents.argtypes = [C.POINTER(AaPackLatents), C.c_void_p]
-    lib.aa_cfg_dpm_step_tokens.argtypes = [C.POINTER(AaDpmStepTok), C.c_void_p]
-    lib.aa_blend.argtypes = [C.POINTER(AaBlend), C.c_void_p]
-    lib.aa_pack_frames.argtypes = [C.POINTER(AaPackFrames), C.c_void_p]
-    lib.aa_cfg_euler_step_tokens.argtypes = [C.POINTER(AaEulerStepTok), C.c_void_p]
-    lib.aa_cfg_ddim_step_tokens.argtypes = [C.POINTER(AaDdimStepTok), C.c_void_p]
-    lib.aa_cfg_unipc_step_tokens.argtypes = [C.POINTER(AaUnipcStepTok), C.c_void_p]
-    lib.aa_freeu_tokens.argtypes = [C.POINTER(AaFreeU), C.c_void_p]
-    lib.aa_cfg_rescale_workspace.argtypes = [C.POINTER(AaCfgRescale)]
-    lib.aa_cfg_rescale_workspace.restype = C.c_size_t
-    lib.aa_cfg_rescale_tokens.argtypes = [C.POINTER(AaCfgRescale), C.c_void_p, C.c_size_t, C.c_void_p]
-    lib.aa_window_gather_latents.argtypes = [C.POINTER(AaWindowGather), C.c_void_p]
-    lib.aa_window_merge_tokens.argtypes = [C.POINTER(AaWindowMerge), C.c_void_p]
-    for s in SYMBOLS[5:]:
-        if s not in ("aa_groupnorm_workspace", "aa_conv_gemm_workspace", "aa_cfg_rescale_workspace"):
-            getattr(lib, s).restype = C.c_int
+    for name, (restype, argtypes) in PROTOTYPES.items():
+        if not hasattr(lib, name):
+            raise RuntimeError(f"{path} does not export {name}")
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = restype, argtypes
     return lib
 
 

@@ -151,7 +151,7 @@ def _ticket_array(t: torch.Tensor):
     graphs of one device run one at a time in this package).  Never allocated inside a capture: a call captured before any eager
     call on that device gets None (partials + reduce launch)."""
     if not t.is_cuda:
-        if not _lib.host_pointers_ok():
+        if not _addressable(t):
             return None
         a = _tickets.get("host")
         if a is None:
@@ -300,14 +300,30 @@ def _ptr(t: Optional[torch.Tensor]):
     return None if t is None else C.c_void_p(t.data_ptr())
 
 
-def _check(*tensors):
+def _addressable(t: torch.Tensor) -> bool:      # on the GPU - or anywhere, while the library in use takes host pointers (the tests' emulator build)
+    return t.is_cuda or _lib.host_pointers_ok()
+
+
+def _check(*tensors, contiguous=True):
     for t in tensors:
         if t is None:
             continue
-        if not t.is_cuda and not _lib.host_pointers_ok():
+        if not _addressable(t):
             raise RuntimeError("animate_anything_amd ops run on the GPU only (tensor is on %s)" % t.device)
-        if not t.is_contiguous():
+        if contiguous and not t.is_contiguous():
             raise RuntimeError("animate_anything_amd ops need contiguous tensors")
+
+
+def _check_token_matrix(op, name, t, ref, how_many, device_of=None, rows=None, channels=0):
+    """One token-matrix operand `name` of `op`: 2-d, rows contiguous (they may be pitched), fp16 / bf16 and of `ref`'s dtype (`how_many`: "all" /
+    "both", as the message counts the operands); device_of = (name, tensor): on that tensor's device; rows: holds `rows` rows of `channels` channels."""
+    _check(t, contiguous=False)
+    if t.dim() != 2 or (t.shape[1] > 1 and t.stride(1) != 1) or t.dtype != ref.dtype or t.dtype not in (torch.float16, torch.bfloat16):
+        raise RuntimeError(f"{op}: {name} must be a 2-d fp16 / bf16 token matrix with contiguous rows, {how_many} of one dtype")
+    if device_of is not None and t.device != device_of[1].device:
+        raise RuntimeError(f"{op}: {name} is on {t.device}, {device_of[0]} on {device_of[1].device}")
+    if rows is not None and (t.shape[0] < rows or t.shape[1] < channels):
+        raise RuntimeError(f"{op}: {name} {tuple(t.shape)} does not hold {rows} rows of {channels} channels")
 
 
 def _stream(t: torch.Tensor):
@@ -526,7 +542,7 @@ def conv_gemm(x0: torch.Tensor, pw: PackedWeight, g: Geom, x1: Optional[torch.Te
     b = pw.bias if isinstance(bias, str) else bias
     _check(x0, x1, pw.w, b, residual, out)
     if rowvec is not None:                                 # may be a column slice of a wider matrix (row pitch = stride(0))
-        if (not rowvec.is_cuda and not _lib.host_pointers_ok()) or rowvec.stride(-1) != 1:
+        if not _addressable(rowvec) or rowvec.stride(-1) != 1:
             raise RuntimeError("conv_gemm: rowvec must be a GPU tensor with contiguous rows")
     c0 = x0.shape[-1]
     c1 = 0 if x1 is None else x1.shape[-1]
@@ -727,7 +743,7 @@ def attention(q: torch.Tensor, q_col0: int, k: torch.Tensor, k_col0: int, v: tor
     row strides of the token matrices; output rows use the q addressing, columns [0, heads*64)."""
     lib = _lib.get()
     for t in (q, k, v):                                   # operands may be column slices of wider matrices (ld = stride(0))
-        if (not t.is_cuda and not _lib.host_pointers_ok()) or t.stride(-1) != 1:
+        if not _addressable(t) or t.stride(-1) != 1:
             raise RuntimeError("attention: operands must be GPU tensors with contiguous rows")
     out = torch.empty(q.shape[0], heads * head_dim, dtype=q.dtype, device=q.device)
     d = AaAttention()
@@ -1243,7 +1259,7 @@ def blend(x: torch.Tensor, y: Optional[torch.Tensor] = None, a: float = 1.0, b: 
     """act(a*x + b*y + rowvec[(row // rowvec_div) % rowvec_mod]) on [rows, C] token matrices (diffusers AlphaBlender etc.)."""
     lib = _lib.get()
     _check(x, y, out)
-    if rowvec is not None and ((not rowvec.is_cuda and not _lib.host_pointers_ok()) or rowvec.stride(-1) != 1):
+    if rowvec is not None and (not _addressable(rowvec) or rowvec.stride(-1) != 1):
         raise RuntimeError("blend: rowvec must be a GPU tensor with contiguous rows")
     o = torch.empty_like(x) if out is None else out
     d = AaBlend()
@@ -1370,10 +1386,7 @@ def freeu(hidden: torch.Tensor, skip: torch.Tensor, images: int, h: int, w: int,
     for name, t in (("hidden", hidden), ("skip", skip), ("hidden_out", hidden_out), ("skip_out", skip_out)):
         if t is None:
             continue
-        if not t.is_cuda and not _lib.host_pointers_ok():
-            raise RuntimeError("animate_anything_amd ops run on the GPU only (tensor is on %s)" % t.device)
-        if t.dim() != 2 or (t.shape[1] > 1 and t.stride(1) != 1) or t.dtype != hidden.dtype or t.dtype not in (torch.float16, torch.bfloat16):
-            raise RuntimeError(f"freeu: {name} must be a 2-d fp16 / bf16 token matrix with contiguous rows, all of one dtype")
+        _check_token_matrix("freeu", name, t, hidden, "all")
         if h >= 1 and w >= 1 and images >= 1 and t.shape[0] != rows:
             raise RuntimeError(f"freeu: {name} has {t.shape[0]} rows, images * h * w = {rows}")
     ho = torch.empty(hidden.shape, dtype=hidden.dtype, device=hidden.device) if hidden_out is None else hidden_out
@@ -1407,15 +1420,8 @@ def cfg_rescale_tokens(tokens: torch.Tensor, clips: int, channels: int, frames: 
     rows = clips * (frames + 1) * hw
     if out is None:
         out = tokens[:max(rows, 0)] if tokens.dim() == 2 else tokens
-    for name, t, need in (("tokens", tokens, 2 * rows), ("out", out, rows)):
-        if not t.is_cuda and not _lib.host_pointers_ok():
-            raise RuntimeError("animate_anything_amd ops run on the GPU only (tensor is on %s)" % t.device)
-        if t.dim() != 2 or (t.shape[1] > 1 and t.stride(1) != 1) or t.dtype != tokens.dtype or t.dtype not in (torch.float16, torch.bfloat16):
-            raise RuntimeError(f"cfg_rescale_tokens: {name} must be a 2-d fp16 / bf16 token matrix with contiguous rows, both of one dtype")
-        if t.device != tokens.device:
-            raise RuntimeError(f"cfg_rescale_tokens: {name} is on {t.device}, tokens on {tokens.device}")
-        if min(clips, channels, frames, hw) >= 1 and (t.shape[0] < need or t.shape[1] < channels):
-            raise RuntimeError(f"cfg_rescale_tokens: {name} {tuple(t.shape)} does not hold {need} rows of {channels} channels")
+    for name, t, need in (("tokens", tokens, 2 * rows), ("out", out, rows)):        # (a bad geometry is the entry point's to refuse)
+        _check_token_matrix("cfg_rescale_tokens", name, t, tokens, "both", ("tokens", tokens), need if min(clips, channels, frames, hw) >= 1 else None, channels)
     if factor is not None:
         _check(factor)
         if factor.dtype != torch.float32 or factor.numel() != max(clips, 0) or factor.device != tokens.device:
@@ -1489,14 +1495,7 @@ def window_merge_tokens(tokens: torch.Tensor, acc: torch.Tensor, merged: torch.T
     clips, frames, hw, c = acc.shape
     halves = 2 if guidance is not None else 1
     for name, t, need in (("tokens", tokens, halves * clips * (w.window_frames + 1) * hw), ("merged", merged, halves * clips * (frames + 1) * hw)):
-        if not t.is_cuda and not _lib.host_pointers_ok():
-            raise RuntimeError("animate_anything_amd ops run on the GPU only (tensor is on %s)" % t.device)
-        if t.dim() != 2 or (t.shape[1] > 1 and t.stride(1) != 1) or t.dtype != tokens.dtype or t.dtype not in (torch.float16, torch.bfloat16):
-            raise RuntimeError(f"window_merge_tokens: {name} must be a 2-d fp16 / bf16 token matrix with contiguous rows, both of one dtype")
-        if t.device != acc.device:
-            raise RuntimeError(f"window_merge_tokens: {name} is on {t.device}, acc on {acc.device}")
-        if t.shape[0] < need or t.shape[1] < c:
-            raise RuntimeError(f"window_merge_tokens: {name} {tuple(t.shape)} does not hold {need} rows of {c} channels")
+        _check_token_matrix("window_merge_tokens", name, t, tokens, "both", ("acc", acc), need, c)
     d = AaWindowMerge()
     d.tokens, d.acc, d.merged = _ptr(tokens), _ptr(acc), _ptr(merged)
     d.clips, d.channels, d.total_frames, d.hw = clips, c, frames, hw

@@ -41,6 +41,58 @@ def test_library_exports_every_declared_symbol():
     assert n >= 20 and bound.aa_conv_gemm_tile_info(-1, info) == -1
 
 
+def _header_text():
+    text = open(os.path.join(ROOT, "include", "aa_mi355.h")).read()
+    return re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+
+
+def _structures():
+    return {n: c for n, c in vars(_lib).items() if isinstance(c, type) and issubclass(c, ctypes.Structure) and c is not ctypes.Structure}
+
+
+def test_structures_have_the_header_layout(tmp_path):
+    """Every ctypes.Structure of _lib against include/aa_mi355.h: the same set of names as the header's `typedef struct`s, and the
+    size and every field offset the host C compiler gives them (a field added on one side only would shift descriptors silently)."""
+    import shutil
+    import subprocess
+    structs = _structures()
+    assert set(structs) == set(re.findall(r"typedef\s+struct\s+(\w+)", _header_text()))
+    cc = next((c for c in (os.environ.get("CC"), "cc", "gcc", "clang") if c and shutil.which(c)), None)
+    if cc is None:
+        pytest.skip("no host C compiler found")
+    lines = ["#include <stdio.h>", "#include <stddef.h>", '#include "aa_mi355.h"', "int main(void) {"]
+    expected = []
+    for name, cls in sorted(structs.items()):
+        lines.append(f'    printf("{name} %zu\\n", sizeof({name}));')
+        expected.append(f"{name} {ctypes.sizeof(cls)}")
+        for field, *_ in cls._fields_:
+            lines.append(f'    printf("{name}.{field} %zu\\n", offsetof({name}, {field}));')
+            expected.append(f"{name}.{field} {getattr(cls, field).offset}")
+    lines += ["    return 0;", "}"]
+    src, exe = tmp_path / "layout.c", tmp_path / "layout"
+    src.write_text("\n".join(lines) + "\n")
+    subprocess.run([cc, "-std=c99", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
+    got = subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.split("\n")[:-1]
+    assert len(expected) > 300                              # (22 structures, 371 fields when this test was written)
+    assert [g for g, e in zip(got, expected) if g != e] == [] and len(got) == len(expected)
+
+
+def test_prototype_table_matches_the_header():
+    """_lib.PROTOTYPES against the header's declarations: the same functions, as many arguments each ((void) = 0), and every return
+    type that is not int stated as such (an `int` read for a void or a 64-bit size_t is the slip a defaulted restype invites)."""
+    decls = {m.group(2): (" ".join(m.group(1).split()), m.group(3))
+             for m in re.finditer(r"^([A-Za-z_][\w \t]*?[\s*]+)(aa_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", _header_text(), flags=re.M)}
+    assert set(decls) == set(declared_symbols()) == set(_lib.PROTOTYPES)
+    restypes = {"void": None, "size_t": ctypes.c_size_t, "const char*": ctypes.c_char_p, "int": ctypes.c_int}
+    for name, (ret, params) in decls.items():
+        restype, argtypes = _lib.PROTOTYPES[name]
+        n_params = 0 if params.strip() in ("void", "") else len(params.split(","))
+        assert len(argtypes) == n_params, (name, params)
+        assert ret.replace(" *", "*") in restypes, (name, ret)
+        assert restype is restypes[ret.replace(" *", "*")], (name, ret, restype)
+    assert list(_lib.SYMBOLS) == list(_lib.PROTOTYPES)
+
+
 def test_missing_library_fails_loudly(tmp_path):
     try:
         _lib.bind(str(tmp_path / "libaa_mi355.so"))
