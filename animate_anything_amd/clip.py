@@ -12,15 +12,14 @@ container: the parity tests compare it with `transformers.CLIPTextModel` itself.
 """
 from __future__ import annotations
 
-import json
-import os
 from types import SimpleNamespace
 
 import torch
 import torch.nn as nn
 
-from . import _lib, ops
+from . import ops
 from ._lib import AA_ACT_GELU, AA_ACT_QUICK_GELU
+from ._model import PretrainedModel
 from .layers import LayerNorm, Linear, weights_key
 
 _ACTS = {"gelu": AA_ACT_GELU, "quick_gelu": AA_ACT_QUICK_GELU}
@@ -111,8 +110,13 @@ class _TextTransformer(nn.Module):
         self.final_layer_norm = LayerNorm(cfg.hidden_size, eps=cfg.layer_norm_eps)
 
 
-class CLIPTextModel(nn.Module):
-    config_name = "config.json"
+class CLIPTextModel(PretrainedModel):
+    """transformers directory layout: config.json + model.safetensors / pytorch_model.bin."""
+
+    class_name = "CLIPTextModel"
+    config_extra = {"architectures": ["CLIPTextModel"], "model_type": "clip_text_model"}
+    config_section = "text_config"
+    weights_name, weights_bin_name = "model", "pytorch_model"
 
     def __init__(self, vocab_size=49408, hidden_size=1024, intermediate_size=4096, num_hidden_layers=23, num_attention_heads=16,
                  max_position_embeddings=77, hidden_act="gelu", layer_norm_eps=1e-5, eos_token_id=2, **_):
@@ -125,40 +129,11 @@ class CLIPTextModel(nn.Module):
                                       layer_norm_eps=layer_norm_eps, eos_token_id=eos_token_id)
         self.text_model = _TextTransformer(self.config)
 
-    @property
-    def dtype(self):
-        return next(self.parameters()).dtype
-
-    @property
-    def device(self):
-        return next(self.parameters()).device
-
     def load_state_dict(self, state_dict, strict=True, **k):
         state_dict = {n: v for n, v in state_dict.items() if not n.endswith("position_ids")}    # buffer of older checkpoints
         if state_dict and not any(n.startswith("text_model.") for n in state_dict):            # transformers >= 5 writes the keys
             state_dict = {"text_model." + n: v for n, v in state_dict.items()}                 # without the `text_model.` level
         return super().load_state_dict(state_dict, strict=strict, **k)
-
-    @classmethod
-    def from_pretrained(cls, path, subfolder=None, torch_dtype=None, variant=None, **overrides):
-        """transformers directory layout: config.json + model.safetensors / pytorch_model.bin."""
-        root = os.path.join(path, subfolder) if subfolder else path
-        with open(os.path.join(root, cls.config_name)) as f:
-            cfg = {k: v for k, v in json.load(f).items() if not k.startswith("_")}
-        cfg = dict(cfg.get("text_config") or {}, **{k: v for k, v in cfg.items() if k != "text_config"})
-        cfg.update(overrides)
-        model = cls(**cfg)
-        from ._ckpt import load_state
-        state = load_state(root, "model", variant, "pytorch_model")
-        model.load_state_dict(state)
-        return model.to(torch_dtype) if torch_dtype is not None else model
-
-    def save_pretrained(self, path):
-        os.makedirs(path, exist_ok=True)
-        with open(os.path.join(path, self.config_name), "w") as f:
-            json.dump(dict(vars(self.config), architectures=["CLIPTextModel"], model_type="clip_text_model"), f, indent=2)
-        from safetensors.torch import save_file
-        save_file({k: v.contiguous().cpu() for k, v in self.state_dict().items()}, os.path.join(path, "model.safetensors"))
 
     def gradient_checkpointing_enable(self):        # inference-only implementation: accepted, no effect (train.py:110-114)
         return None
@@ -169,8 +144,7 @@ class CLIPTextModel(nn.Module):
     def forward(self, input_ids, attention_mask=None, position_ids=None, **_):
         """input_ids [B, L] (L <= max_position_embeddings) -> (last_hidden_state [B, L, D], pooler_output [B, D]).
         `attention_mask` is accepted and, like the reference's call (no mask is passed, padding attends causally), unused."""
-        if not input_ids.is_cuda and not _lib.host_pointers_ok():
-            raise RuntimeError("animate_anything_amd.CLIPTextModel runs on the GPU only (no CPU fallback)")
+        self.require_device(input_ids)
         tm = self.text_model
         b, length = input_ids.shape
         pos = torch.arange(length, device=input_ids.device) if position_ids is None else position_ids.reshape(-1)[:length]
@@ -211,14 +185,17 @@ class _VisionTransformer(nn.Module):
         self.post_layernorm = LayerNorm(cfg.hidden_size, eps=cfg.layer_norm_eps)
 
 
-class CLIPVisionModelWithProjection(nn.Module):
+class CLIPVisionModelWithProjection(PretrainedModel):
     """Drop-in for the `transformers` `CLIPVisionModelWithProjection` that diffusers' StableVideoDiffusionPipeline carries as
     `image_encoder` (loaded with the pipeline at /root/reference/train_svd.py:85-91, called once per clip by `_encode_image`):
     `model(pixel_values).image_embeds`.  ViT-H/14 (1280 wide, 32 layers, 16 heads of 80 channels, gelu) and ViT-L/14 (1024 wide,
     heads of 64).  The 14x14 / stride-14 patch embedding is the implicit-GEMM contraction over the 3-channel image padded to 8
     channels; attention is not causal; the class token's final state goes through `post_layernorm` and `visual_projection`."""
 
-    config_name = "config.json"
+    class_name = "CLIPVisionModelWithProjection"
+    config_extra = {"architectures": ["CLIPVisionModelWithProjection"], "model_type": "clip_vision_model"}
+    config_section = "vision_config"
+    weights_name, weights_bin_name = "model", "pytorch_model"
 
     def __init__(self, hidden_size=1280, intermediate_size=5120, projection_dim=1024, num_hidden_layers=32, num_attention_heads=16,
                  num_channels=3, image_size=224, patch_size=14, hidden_act="gelu", layer_norm_eps=1e-5, **_):
@@ -234,42 +211,13 @@ class CLIPVisionModelWithProjection(nn.Module):
         self.vision_model = _VisionTransformer(self.config)
         self.visual_projection = Linear(hidden_size, projection_dim, bias=False)
 
-    @property
-    def dtype(self):
-        return next(self.parameters()).dtype
-
-    @property
-    def device(self):
-        return next(self.parameters()).device
-
     def load_state_dict(self, state_dict, strict=True, **k):
         state_dict = {n: v for n, v in state_dict.items() if not n.endswith("position_ids")}
         return super().load_state_dict(state_dict, strict=strict, **k)
 
-    @classmethod
-    def from_pretrained(cls, path, subfolder=None, torch_dtype=None, variant=None, **overrides):
-        root = os.path.join(path, subfolder) if subfolder else path
-        with open(os.path.join(root, cls.config_name)) as f:
-            cfg = {k: v for k, v in json.load(f).items() if not k.startswith("_")}
-        cfg = dict(cfg.get("vision_config") or {}, **{k: v for k, v in cfg.items() if k != "vision_config"})
-        cfg.update(overrides)
-        model = cls(**cfg)
-        from ._ckpt import load_state
-        state = load_state(root, "model", variant, "pytorch_model")
-        model.load_state_dict(state)
-        return model.to(torch_dtype) if torch_dtype is not None else model
-
-    def save_pretrained(self, path):
-        os.makedirs(path, exist_ok=True)
-        with open(os.path.join(path, self.config_name), "w") as f:
-            json.dump(dict(vars(self.config), architectures=["CLIPVisionModelWithProjection"], model_type="clip_vision_model"), f, indent=2)
-        from safetensors.torch import save_file
-        save_file({k: v.contiguous().cpu() for k, v in self.state_dict().items()}, os.path.join(path, "model.safetensors"))
-
     def forward(self, pixel_values, **_):
         """pixel_values [B, 3, image_size, image_size] (CLIP-normalised) -> .image_embeds [B, projection_dim]."""
-        if not pixel_values.is_cuda and not _lib.host_pointers_ok():
-            raise RuntimeError("animate_anything_amd.CLIPVisionModelWithProjection runs on the GPU only (no CPU fallback)")
+        self.require_device(pixel_values)
         cfg, vm = self.config, self.vision_model
         b, c, h, w = pixel_values.shape
         if h != cfg.image_size or w != cfg.image_size:

@@ -15,8 +15,9 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from . import _lib, ops
+from . import ops
 from ._lib import AA_ACT_NONE, AA_ACT_SILU
+from ._model import require_device
 from .layers import Conv2d, Downsample2D, Grid, GroupNorm, Linear, ResnetBlock2D, Upsample2D
 from .pipeline import LatentToVideoPipeline, tensor2vid
 from .vae import _to_tokens8
@@ -24,11 +25,6 @@ from .vae import _to_tokens8
 
 def _nchw(tokens, n, h, w):
     return tokens.reshape(n, h, w, -1).permute(0, 3, 1, 2)
-
-
-def _check_device(x):
-    if not x.is_cuda and not _lib.host_pointers_ok():
-        raise RuntimeError("animate_anything_amd.layerdiffuse runs on the GPU only (no CPU fallback)")
 
 
 class LatentTransparencyOffsetEncoder(nn.Module):
@@ -46,7 +42,7 @@ class LatentTransparencyOffsetEncoder(nn.Module):
         self.blocks = nn.Sequential(*mods, last)
 
     def forward(self, x):
-        _check_device(x)
+        require_device(x, "layerdiffuse")
         n, _, h, w = x.shape
         dt = self.blocks[0].weight.dtype
         t = _to_tokens8(x.to(dt))
@@ -155,7 +151,7 @@ class UNet384(nn.Module):
         return self.conv_in.weight.dtype
 
     def forward(self, x, latent):
-        _check_device(x)
+        require_device(x, "layerdiffuse")
         n, _, h, w = x.shape
         dt = self.dtype
         g = Grid(1, n, h, w)

@@ -10,14 +10,13 @@ cat / chunk / permute / scheduler.step chain (pipeline.py:165-192) collapses int
 """
 from __future__ import annotations
 
-import json
-import os
 from types import SimpleNamespace
 
 import numpy as np
 import torch
 
 from . import ops
+from ._model import PretrainedPipeline, read_scheduler_config
 from .schedulers import CONTEXT_WEIGHTS, DDIMScheduler, DPMSolverMultistepScheduler, UniPCMultistepScheduler, context_windows
 
 
@@ -149,7 +148,13 @@ def tensor2vid(video):
     return [fr for fr in frames]
 
 
-class LatentToVideoPipeline:
+class LatentToVideoPipeline(PretrainedPipeline):
+    """`save_pretrained` (reference train.py:298-299; text_encoder/ + tokenizer/ through transformers when present) and `to`:
+    _model.PretrainedPipeline."""
+
+    class_name = "LatentToVideoPipeline"
+    components = ("unet", "vae", "text_encoder", "tokenizer")
+    on_device = ("vae", "unet", "text_encoder")
     cfg_shared_prefix = True     # compute the text-independent prefix of the UNet once per guidance pair: the same arithmetic per element, but
                                  # other tile shapes / summation orders in the shared part - the two forms differ inside the fp16 noise floor
                                  # (0.013-0.029 of the latents' range over three steps at guidance 9, tests/test_gpu_fullsize.py), not bit for bit
@@ -174,8 +179,7 @@ class LatentToVideoPipeline:
         if vae is None:
             vae = AutoencoderKL.from_pretrained(path, subfolder="vae")
         if scheduler is None:
-            cfg_path = os.path.join(path, "scheduler", "scheduler_config.json")
-            cfg = json.load(open(cfg_path)) if os.path.exists(cfg_path) else {}
+            cfg = read_scheduler_config(path)
             named = {"DDIMScheduler": DDIMScheduler, "UniPCMultistepScheduler": UniPCMultistepScheduler}
             kind = named.get(cfg.get("_class_name"), DPMSolverMultistepScheduler) if scheduler_from_config else DPMSolverMultistepScheduler
             scheduler = kind.from_config(cfg)
@@ -188,32 +192,6 @@ class LatentToVideoPipeline:
             except Exception:      # text encoder is optional: callers may pass prompt_embeds
                 pass
         return cls(vae, text_encoder, tokenizer, unet, scheduler)
-
-    def save_pretrained(self, path):
-        """diffusers directory layout (what `from_pretrained` reads; reference train.py:298-299): unet/, vae/,
-        scheduler/scheduler_config.json, text_encoder/ + tokenizer/ through transformers when present, model_index.json."""
-        os.makedirs(path, exist_ok=True)
-        index = {"_class_name": "LatentToVideoPipeline"}
-        for name in ("unet", "vae", "text_encoder", "tokenizer"):
-            m = getattr(self, name)
-            if m is not None and hasattr(m, "save_pretrained"):
-                m.save_pretrained(os.path.join(path, name))
-                index[name] = [type(m).__module__.split(".")[0], type(m).__name__]
-        os.makedirs(os.path.join(path, "scheduler"), exist_ok=True)
-        with open(os.path.join(path, "scheduler", "scheduler_config.json"), "w") as f:
-            json.dump(dict(vars(self.scheduler.config), _class_name=type(self.scheduler).__name__), f, indent=2)
-        index["scheduler"] = ["animate_anything_amd", type(self.scheduler).__name__]
-        with open(os.path.join(path, "model_index.json"), "w") as f:
-            json.dump(index, f, indent=2)
-
-    def to(self, device=None, torch_dtype=None, **_):
-        for m in (self.vae, self.unet, self.text_encoder):
-            if m is not None:
-                if device is not None:
-                    m.to(device)
-                if torch_dtype is not None:
-                    m.to(torch_dtype)
-        return self
 
     def enable_freeu(self, s1, s2, b1, b2):
         """diffusers `TextToVideoSDPipeline.enable_freeu`: forwards to the UNet (UNet3DConditionModel.enable_freeu)."""

@@ -13,8 +13,6 @@ module passed by the caller works as well).
 """
 from __future__ import annotations
 
-import json
-import os
 from types import SimpleNamespace
 
 import numpy as np
@@ -22,6 +20,7 @@ import torch
 import torch.nn.functional as F
 
 from . import ops
+from ._model import PretrainedPipeline, read_scheduler_config
 from .schedulers import EulerDiscreteScheduler
 
 
@@ -110,8 +109,14 @@ def tensor2vid(video, processor, output_type="np"):
     return outputs
 
 
-class StableVideoDiffusionPipeline:
-    """The diffusers base class, as far as the reference's two subclasses use it."""
+class StableVideoDiffusionPipeline(PretrainedPipeline):
+    """The diffusers base class, as far as the reference's two subclasses use it.  `save_pretrained` (reference
+    train_svd.py:103,320-321; image_encoder/ + feature_extractor/ through transformers when present) and `to`:
+    _model.PretrainedPipeline."""
+
+    class_name = "StableVideoDiffusionPipeline"
+    components = ("unet", "vae", "image_encoder", "feature_extractor")
+    on_device = ("vae", "unet", "image_encoder")
 
     fused_step = True     # False: the reference's own per-step sequence (module forward, torch guidance, scheduler.step)
 
@@ -132,8 +137,7 @@ class StableVideoDiffusionPipeline:
         if vae is None:
             vae = AutoencoderKLTemporalDecoder.from_pretrained(path, subfolder="vae", torch_dtype=torch_dtype, variant=variant)
         if scheduler is None:
-            cfg_path = os.path.join(path, "scheduler", "scheduler_config.json")
-            scheduler = EulerDiscreteScheduler.from_config(json.load(open(cfg_path)) if os.path.exists(cfg_path) else {})
+            scheduler = EulerDiscreteScheduler.from_config(read_scheduler_config(path))
         feature_extractor = None   # (`_encode_image` applies the CLIP resize / normalisation itself)
         if image_encoder is None:
             try:
@@ -142,32 +146,6 @@ class StableVideoDiffusionPipeline:
             except Exception:      # optional: callers may pass image_embeddings
                 pass
         return cls(vae, image_encoder, unet, scheduler, feature_extractor)
-
-    def save_pretrained(self, path):
-        """diffusers directory layout (what `from_pretrained` reads; reference train_svd.py:103,320-321): unet/, vae/,
-        scheduler/scheduler_config.json, image_encoder/ + feature_extractor/ through transformers when present."""
-        os.makedirs(path, exist_ok=True)
-        index = {"_class_name": "StableVideoDiffusionPipeline"}
-        for name in ("unet", "vae", "image_encoder", "feature_extractor"):
-            m = getattr(self, name)
-            if m is not None and hasattr(m, "save_pretrained"):
-                m.save_pretrained(os.path.join(path, name))
-                index[name] = [type(m).__module__.split(".")[0], type(m).__name__]
-        os.makedirs(os.path.join(path, "scheduler"), exist_ok=True)
-        with open(os.path.join(path, "scheduler", "scheduler_config.json"), "w") as f:
-            json.dump(dict(vars(self.scheduler.config), _class_name=type(self.scheduler).__name__), f, indent=2)
-        index["scheduler"] = ["animate_anything_amd", type(self.scheduler).__name__]
-        with open(os.path.join(path, "model_index.json"), "w") as f:
-            json.dump(index, f, indent=2)
-
-    def to(self, device=None, torch_dtype=None, **_):
-        for m in (self.vae, self.unet, self.image_encoder):
-            if m is not None:
-                if device is not None:
-                    m.to(device)
-                if torch_dtype is not None:
-                    m.to(torch_dtype)
-        return self
 
     @property
     def guidance_scale(self):

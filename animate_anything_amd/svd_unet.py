@@ -17,15 +17,14 @@ channels-last token matrix ordered (clip, frame, y, x) serves the per-frame and 
 """
 from __future__ import annotations
 
-import json
-import os
 from types import SimpleNamespace
 
 import torch
 import torch.nn as nn
 
-from . import _lib, ops
+from . import ops
 from ._lib import AA_ACT_SILU
+from ._model import GraphModel, Session
 from .layers import (Attention, BasicTransformerBlock, Conv2d, Conv3d, Downsample2D, FeedForward, Grid, GroupNorm,
                      LayerNorm, Linear, ResnetBlock2D, TimestepEmbedding, Upsample2D, weights_key)
 
@@ -289,12 +288,14 @@ _DOWN = {"CrossAttnDownBlockSpatioTemporal": CrossAttnDownBlockSpatioTemporal, "
 _UP = {"CrossAttnUpBlockSpatioTemporal": CrossAttnUpBlockSpatioTemporal, "UpBlockSpatioTemporal": UpBlockSpatioTemporal}
 
 
-class UNetSpatioTemporalConditionModel(nn.Module):
+class UNetSpatioTemporalConditionModel(GraphModel):
     """Constructor arguments / defaults: diffusers UNetSpatioTemporalConditionModel (stable-video-diffusion-img2vid config);
     the reference instantiates it with in_channels=9 (train_svd.py:93-99).  GroupNorm epsilons per block type follow the
-    diffusers blocks: 1e-6 in CrossAttnDownBlockSpatioTemporal, 1e-5 elsewhere (restated from memory)."""
+    diffusers blocks: 1e-6 in CrossAttnDownBlockSpatioTemporal, 1e-5 elsewhere (restated from memory).
+    Loading, saving, `enable_graph`, `invalidate_caches` and the session store: _model.GraphModel."""
 
-    config_name = "config.json"
+    class_name = "UNetSpatioTemporalConditionModel"
+    config_extra = {"_class_name": "UNetSpatioTemporalConditionModel"}
     _supports_gradient_checkpointing = True
 
     def __init__(self, sample_size=None, in_channels=8, out_channels=4,
@@ -366,32 +367,6 @@ class UNetSpatioTemporalConditionModel(nn.Module):
         self._graph = None
         self._packed_channels = 8 if in_channels <= 8 else 16
 
-    # ------------------------------------------------------------------ nn.Module / diffusers protocol
-    @property
-    def dtype(self):
-        return next(self.parameters()).dtype
-
-    @property
-    def device(self):
-        return next(self.parameters()).device
-
-    def _apply(self, fn, *a, **k):
-        self.invalidate_caches()
-        return super()._apply(fn, *a, **k)
-
-    def invalidate_caches(self):
-        """Drop the derived copies of the weights (batched projection packs, captured hipGraphs); see
-        UNet3DConditionModel.invalidate_caches."""
-        self._temb_pack = None
-        self._text_pack = None
-        if getattr(self, "_graph", None) is not None:
-            self._graph = {}
-
-    def load_state_dict(self, *a, **k):
-        out = super().load_state_dict(*a, **k)
-        self.invalidate_caches()
-        return out
-
     def enable_gradient_checkpointing(self):
         return None
 
@@ -401,72 +376,17 @@ class UNetSpatioTemporalConditionModel(nn.Module):
     def enable_xformers_memory_efficient_attention(self, *a, **k):
         return None
 
-    @classmethod
-    def from_config(cls, config: dict, **overrides):
-        cfg = {k: v for k, v in dict(config).items() if not k.startswith("_")}
-        cfg.update(overrides)
-        import inspect
-        ok = set(inspect.signature(cls.__init__).parameters) - {"self"}
-        return cls(**{k: v for k, v in cfg.items() if k in ok})
-
-    @classmethod
-    def from_pretrained(cls, path, subfolder=None, torch_dtype=None, variant=None, **overrides):
-        root = os.path.join(path, subfolder) if subfolder else path
-        with open(os.path.join(root, cls.config_name)) as f:
-            model = cls.from_config(json.load(f), **overrides)
-        from ._ckpt import load_state
-        state = load_state(root, "diffusion_pytorch_model", variant)
-        model.load_state_dict(state)
-        return model.to(torch_dtype) if torch_dtype is not None else model
-
-    def save_pretrained(self, path):
-        os.makedirs(path, exist_ok=True)
-        with open(os.path.join(path, self.config_name), "w") as f:
-            json.dump(dict(vars(self.config), _class_name="UNetSpatioTemporalConditionModel"), f, indent=2)
-        from safetensors.torch import save_file
-        save_file({k: v.contiguous().cpu() for k, v in self.state_dict().items()},
-                  os.path.join(path, "diffusion_pytorch_model.safetensors"))
-
-    # ------------------------------------------------------------------ batched small projections
+    # ------------------------------------------------------------------ batched small projections (_model.GraphModel)
     def _project_text(self, text_tokens):
         """K | V of the context for every cross-attention layer (spatial and temporal) as ONE contraction."""
-        if getattr(self, "_text_layers", None) is None:
-            self._text_layers = [m for m in self.modules() if isinstance(m, Attention) and m.is_cross]
-        key = weights_key(*[w_ for a in self._text_layers for w_ in (a.to_k.weight, a.to_v.weight)])
-        if getattr(self, "_text_pack", None) is None or self._text_key != key:
-            self._text_key = key
-            layers_ = self._text_layers
-            w = torch.cat([torch.cat([a.to_k.weight.detach(), a.to_v.weight.detach()], dim=0) for a in layers_], dim=0)
-            offs, o = [], 0
-            for a in layers_:
-                offs.append(o)
-                o += 2 * a.inner
-            self._text_pack = (ops.pack_weight(w), layers_, offs)
-        pw, layers_, offs = self._text_pack
-        proj = ops.conv_gemm(text_tokens, pw, ops.linear_geom(text_tokens.shape[0]))
-        for a, o in zip(layers_, offs):
-            a.kv = proj[:, o:o + 2 * a.inner]
+        self._project_batched(text_tokens, "_text_pack", lambda m: isinstance(m, Attention) and m.is_cross,
+                              lambda a: (a.to_k, a.to_v), "kv")
 
     def _project_time_embeddings(self, temb_silu):
         """time_emb_proj of every spatial and temporal resnet as ONE contraction; each block receives its column slice."""
-        if getattr(self, "_temb_blocks", None) is None:
-            self._temb_blocks = [m for m in self.modules()
-                                 if isinstance(m, (ResnetBlock2D, TemporalResnetBlock)) and m.time_emb_proj is not None]
-        key = weights_key(*[w_ for b in self._temb_blocks for w_ in (b.time_emb_proj.weight, b.time_emb_proj.bias)])
-        if getattr(self, "_temb_pack", None) is None or self._temb_key != key:
-            self._temb_key = key
-            blocks = self._temb_blocks
-            w = torch.cat([b.time_emb_proj.weight.detach() for b in blocks], dim=0)
-            bias = torch.cat([b.time_emb_proj.bias.detach() for b in blocks], dim=0)
-            offs, o = [], 0
-            for b in blocks:
-                offs.append(o)
-                o += b.time_emb_proj.weight.shape[0]
-            self._temb_pack = (ops.pack_weight(w, bias), blocks, offs)
-        pw, blocks, offs = self._temb_pack
-        proj = ops.conv_gemm(temb_silu, pw, ops.linear_geom(temb_silu.shape[0]))
-        for b, o in zip(blocks, offs):
-            b.tproj = proj[:, o:o + b.time_emb_proj.weight.shape[0]]
+        self._project_batched(temb_silu, "_temb_pack",
+                              lambda m: isinstance(m, (ResnetBlock2D, TemporalResnetBlock)) and m.time_emb_proj is not None,
+                              lambda b: (b.time_emb_proj,), "tproj")
 
     # ------------------------------------------------------------------ hot path
     def _core(self, sources, scale, scaled_src, t, added_time_ids, text_tokens, g: Grid, text_len: int):
@@ -499,8 +419,7 @@ class UNetSpatioTemporalConditionModel(nn.Module):
     def forward(self, sample, timestep, encoder_hidden_states, added_time_ids, return_dict=True):
         """diffusers UNetSpatioTemporalConditionModel.forward: sample [B, F, C, H, W], timestep scalar or [B],
         encoder_hidden_states [B, L, D], added_time_ids [B, 3] -> .sample [B, F, out_channels, H, W]."""
-        if not sample.is_cuda and not _lib.host_pointers_ok():
-            raise RuntimeError("animate_anything_amd.UNetSpatioTemporalConditionModel runs on the GPU only (no CPU fallback)")
+        self.require_device(sample)
         dt, dev = self.dtype, sample.device
         b, frames, c, h, w = sample.shape
         if c != self.config.in_channels:
@@ -518,27 +437,17 @@ class UNetSpatioTemporalConditionModel(nn.Module):
         return UNetSpatioTemporalConditionOutput(sample=y) if return_dict else (y,)
 
     # ------------------------------------------------------------------ sessions: static inputs (+ hipGraph replay)
-    def enable_graph(self, enabled=True):
-        """Capture [embeddings + frame packing + UNet] in a hipGraph on first use per input signature and replay it afterwards."""
-        self._graph = {} if enabled else None
-
     def session(self, batch, frames, h, w, text_shape, sources, device, scaled_src=-1):
         """Static input buffers (and, with graphs enabled, the captured hipGraph) of one input signature.
         `sources`: ((batch_i, channels_i, dtype_i), ...) of the channel-concatenated inputs."""
         key = (batch, frames, h, w, tuple(text_shape), tuple(sources), scaled_src, self.dtype, str(device))
-        store = self._graph if self._graph is not None else self.__dict__.setdefault("_eager_sessions", {})
-        sess = store.get(key)
-        if sess is None:
-            if self._graph is None:
-                store.clear()
-            sess = store[key] = _Session(self, key, device)
-        return sess
+        return self._session(key, device, _Session)
 
 
-class _Session:
+class _Session(Session):
     def __init__(self, net, key, device):
+        super().__init__(net)
         b, frames, h, w, text_shape, sources, self.scaled_src, dt, _dev = key
-        self.net = net
         z = lambda *s, dtype=dt: torch.zeros(*s, dtype=dtype, device=device)
         self.inputs = dict(t=z(b, dtype=torch.float32), ids=z(b, 3, dtype=torch.float32), text=z(b, *text_shape),
                            scale=torch.ones(1, dtype=torch.float32, device=device))
@@ -547,32 +456,9 @@ class _Session:
         self.n_src = len(sources)
         self.text_len = text_shape[0]
         self.grid = Grid(b, frames, h, w)
-        self.graph = None
-        self.out = None
-
-    def load(self, **tensors):
-        for k, v in tensors.items():
-            dst = self.inputs[k]
-            if dst is not None and v is not None and dst.data_ptr() != v.data_ptr():
-                dst.copy_(v.reshape(dst.shape) if v.numel() == dst.numel() else v.expand(dst.shape))
 
     def _core(self):
         i = self.inputs
         srcs = [i[f"src{k}"] for k in range(self.n_src)]
         return self.net._core(srcs, i["scale"] if self.scaled_src >= 0 else None, self.scaled_src, i["t"], i["ids"],
                               i["text"].reshape(-1, i["text"].shape[-1]), self.grid, self.text_len)
-
-    def run(self):
-        if self.net._graph is None:
-            return self._core()
-        if self.graph is None:
-            s = torch.cuda.Stream()
-            s.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(s):                                   # warm-up outside capture (packs weights, autotunes)
-                self._core()
-            torch.cuda.current_stream().wait_stream(s)
-            self.graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self.graph):
-                self.out = self._core()
-        self.graph.replay()
-        return self.out

@@ -9,17 +9,15 @@ over the frames) reads the 3-channel image padded to 8 channels.
 """
 from __future__ import annotations
 
-import json
-import os
 from types import SimpleNamespace
 
 import torch
 import torch.nn as nn
 
-from . import _lib, ops
+from . import ops
 from .layers import Conv2d, Conv3d, Grid, GroupNorm, Upsample2D
 from .svd_unet import SpatioTemporalResBlock
-from .vae import DiagonalGaussianDistribution, Encoder, VaeAttention, _to_tokens8
+from .vae import Encoder, VaeAttention, _KLEncoderModel, _to_tokens8
 
 
 def _st_block(cin, cout):
@@ -88,8 +86,9 @@ class TemporalDecoder(nn.Module):
         return self.time_conv_out.tokens(img8, ops.tconv_geom(g.clips, g.frames, g.hw)), g
 
 
-class AutoencoderKLTemporalDecoder(nn.Module):
-    config_name = "config.json"
+class AutoencoderKLTemporalDecoder(_KLEncoderModel):
+    class_name = "AutoencoderKLTemporalDecoder"
+    config_extra = {"_class_name": "AutoencoderKLTemporalDecoder"}
 
     def __init__(self, in_channels=3, out_channels=3, block_out_channels=(128, 256, 512, 512), layers_per_block=2,
                  latent_channels=4, scaling_factor=0.18215, force_upcast=True, **_):
@@ -103,53 +102,9 @@ class AutoencoderKLTemporalDecoder(nn.Module):
         self.decoder = TemporalDecoder(latent_channels, out_channels, block_out_channels, layers_per_block)
         self.quant_conv = Conv2d(2 * latent_channels, 2 * latent_channels, 1)
 
-    @property
-    def dtype(self):
-        return next(self.parameters()).dtype
-
-    @property
-    def device(self):
-        return next(self.parameters()).device
-
-    @classmethod
-    def from_pretrained(cls, path, subfolder=None, torch_dtype=None, variant=None, **overrides):
-        root = os.path.join(path, subfolder) if subfolder else path
-        with open(os.path.join(root, cls.config_name)) as f:
-            cfg = {k: v for k, v in json.load(f).items() if not k.startswith("_")}
-        cfg.update(overrides)
-        import inspect
-        ok = set(inspect.signature(cls.__init__).parameters) - {"self", "_"}
-        model = cls(**{k: v for k, v in cfg.items() if k in ok})
-        from ._ckpt import load_state
-        state = load_state(root, "diffusion_pytorch_model", variant)
-        model.load_state_dict(state)
-        return model.to(torch_dtype) if torch_dtype is not None else model
-
-    def save_pretrained(self, path):
-        os.makedirs(path, exist_ok=True)
-        with open(os.path.join(path, self.config_name), "w") as f:
-            json.dump(dict(vars(self.config), _class_name="AutoencoderKLTemporalDecoder"), f, indent=2)
-        from safetensors.torch import save_file
-        save_file({k: v.contiguous().cpu() for k, v in self.state_dict().items()},
-                  os.path.join(path, "diffusion_pytorch_model.safetensors"))
-
-    def _guard(self, x):
-        if not x.is_cuda and not _lib.host_pointers_ok():
-            raise RuntimeError("animate_anything_amd.AutoencoderKLTemporalDecoder runs on the GPU only (no CPU fallback)")
-
-    def encode(self, x):
-        """x [N,3,H,W] in [-1,1] -> .latent_dist (DiagonalGaussianDistribution over [N,4,H/8,W/8])."""
-        self._guard(x)
-        x = x.to(self.dtype)
-        n, _, h, w = x.shape
-        m, g = self.encoder.tokens(_to_tokens8(x), Grid(1, n, h, w))
-        m = self.quant_conv.tokens(m, ops.linear_geom(m.shape[0]))
-        moments = m.reshape(n, g.h, g.w, -1).permute(0, 3, 1, 2).contiguous()
-        return SimpleNamespace(latent_dist=DiagonalGaussianDistribution(moments))
-
     def decode(self, z, num_frames=1):
         """z [B*F,4,h,w], F = num_frames consecutive frames per clip -> .sample [B*F,3,8h,8w]."""
-        self._guard(z)
+        self.require_device(z)
         z = z.to(self.dtype)
         n, _, h, w = z.shape
         if n % num_frames:

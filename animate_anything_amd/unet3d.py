@@ -9,8 +9,6 @@ current stream, so it can be captured in a hipGraph (`enable_graph`).
 """
 from __future__ import annotations
 
-import json
-import os
 from dataclasses import dataclass
 from types import SimpleNamespace
 from typing import Optional
@@ -18,8 +16,9 @@ from typing import Optional
 import torch
 import torch.nn as nn
 
-from . import _lib, ops
-from .layers import (Conv2d, Downsample2D, Grid, GroupNorm, Linear, ResnetBlock2D, TemporalConvLayer,
+from . import ops
+from ._model import GraphModel, Session
+from .layers import (Attention, Conv2d, Downsample2D, Grid, GroupNorm, Linear, ResnetBlock2D, TemporalConvLayer,
                      TimestepEmbedding, Transformer2DModel, TransformerTemporalModel, Upsample2D)
 
 
@@ -149,10 +148,13 @@ _DOWN = {"CrossAttnDownBlock3D": CrossAttnDownBlock3D, "DownBlock3D": DownBlock3
 _UP = {"CrossAttnUpBlock3D": CrossAttnUpBlock3D, "UpBlock3D": UpBlock3D}
 
 
-class UNet3DConditionModel(nn.Module):
-    """Constructor arguments / defaults: reference unet_3d_condition_mask.py:87-110."""
+class UNet3DConditionModel(GraphModel):
+    """Constructor arguments / defaults: reference unet_3d_condition_mask.py:87-110.  Loading, saving, `enable_graph`,
+    `invalidate_caches` and the session store: _model.GraphModel."""
 
-    config_name = "config.json"
+    class_name = "UNet3DConditionModel"
+    config_extra = {"_class_name": "UNet3DConditionModel"}
+    _packs = GraphModel._packs + ("_co_pack",)
     _supports_gradient_checkpointing = True
 
     def __init__(self, sample_size=None, in_channels=4, out_channels=4,
@@ -241,76 +243,17 @@ class UNet3DConditionModel(nn.Module):
         if _layers.AA_FP8_FF:                                  # (the module-level knob: see enable_fp8_feedforward)
             self.enable_fp8_feedforward()
 
-    # ------------------------------------------------------------------ nn.Module / diffusers protocol
-    @property
-    def dtype(self):
-        return next(self.parameters()).dtype
-
-    @property
-    def device(self):
-        return next(self.parameters()).device
-
-    def _apply(self, fn, *a, **k):
-        self.invalidate_caches()
-        return super()._apply(fn, *a, **k)
-
-    def invalidate_caches(self):
-        """Drop every derived copy of the weights: the batched time-embedding / text K|V packs and the captured hipGraphs
-        (which replay launches that point at the packed copies).  Called on `.to()` / `load_state_dict()`; call it by hand
-        after editing parameters in place while a graph is enabled (the per-layer packs notice in-place edits themselves,
-        a captured graph cannot)."""
-        self._temb_pack = None
-        self._text_pack = None
-        self._co_pack = None
-        if getattr(self, "_graph", None) is not None:
-            self._graph = {}
-
-    def load_state_dict(self, *a, **k):
-        out = super().load_state_dict(*a, **k)
-        self.invalidate_caches()
-        return out
-
+    # ------------------------------------------------------------------ batched small projections (_model.GraphModel)
     def _project_text(self, text_tokens):
         """K | V of the text for every cross-attention layer as ONE contraction; each layer receives its column slice."""
-        from .layers import Attention, weights_key
-        if getattr(self, "_text_layers", None) is None:
-            self._text_layers = [m for m in self.modules() if isinstance(m, Attention) and m.is_cross]
-        key = weights_key(*[w_ for a in self._text_layers for w_ in (a.to_k.weight, a.to_v.weight)])
-        if getattr(self, "_text_pack", None) is None or self._text_key != key:
-            self._text_key = key
-            layers_ = self._text_layers
-            w = torch.cat([torch.cat([a.to_k.weight.detach(), a.to_v.weight.detach()], dim=0) for a in layers_], dim=0)
-            offs, o = [], 0
-            for a in layers_:
-                offs.append(o)
-                o += 2 * a.inner
-            self._text_pack = (ops.pack_weight(w), layers_, offs)
-        pw, layers_, offs = self._text_pack
-        proj = ops.conv_gemm(text_tokens, pw, ops.linear_geom(text_tokens.shape[0]))       # [clips*L, sum of 2*inner]
-        for a, o in zip(layers_, offs):
-            a.kv = proj[:, o:o + 2 * a.inner]
+        self._project_batched(text_tokens, "_text_pack", lambda m: isinstance(m, Attention) and m.is_cross,
+                              lambda a: (a.to_k, a.to_v), "kv")                          # [clips*L, sum of 2*inner]
 
     def _project_time_embeddings(self, temb_silu):
         """All ResnetBlock2D.time_emb_proj of the network as ONE contraction (31 two-row GEMMs otherwise, each a
         latency-bound launch): rows of the weights concatenated, every block receives its column slice."""
-        from .layers import ResnetBlock2D, weights_key
-        if getattr(self, "_temb_blocks", None) is None:
-            self._temb_blocks = [m for m in self.modules() if isinstance(m, ResnetBlock2D) and m.time_emb_proj is not None]
-        key = weights_key(*[w_ for b in self._temb_blocks for w_ in (b.time_emb_proj.weight, b.time_emb_proj.bias)])
-        if getattr(self, "_temb_pack", None) is None or self._temb_key != key:
-            self._temb_key = key
-            blocks = self._temb_blocks
-            w = torch.cat([b.time_emb_proj.weight.detach() for b in blocks], dim=0)
-            bias = torch.cat([b.time_emb_proj.bias.detach() for b in blocks], dim=0)
-            offs, o = [], 0
-            for b in blocks:
-                offs.append(o)
-                o += b.time_emb_proj.weight.shape[0]
-            self._temb_pack = (ops.pack_weight(w, bias), blocks, offs)
-        pw, blocks, offs = self._temb_pack
-        proj = ops.conv_gemm(temb_silu, pw, ops.linear_geom(temb_silu.shape[0]))            # [clips, sum of Cout]
-        for b, o in zip(blocks, offs):
-            b.tproj = proj[:, o:o + b.time_emb_proj.weight.shape[0]]
+        self._project_batched(temb_silu, "_temb_pack", lambda m: isinstance(m, ResnetBlock2D) and m.time_emb_proj is not None,
+                              lambda b: (b.time_emb_proj,), "tproj")                     # [clips, sum of Cout]
 
     def enable_gradient_checkpointing(self):       # inference-only implementation: accepted, no effect
         self.gradient_checkpointing = True
@@ -323,34 +266,6 @@ class UNet3DConditionModel(nn.Module):
 
     def set_attention_slice(self, slice_size):     # scores never leave the chip: slicing is moot
         return None
-
-    @classmethod
-    def from_config(cls, config: dict, **overrides):
-        cfg = {k: v for k, v in dict(config).items() if not k.startswith("_")}
-        cfg.update(overrides)
-        import inspect
-        ok = set(inspect.signature(cls.__init__).parameters) - {"self"}
-        return cls(**{k: v for k, v in cfg.items() if k in ok})
-
-    @classmethod
-    def from_pretrained(cls, path, subfolder=None, torch_dtype=None, variant=None, **overrides):
-        """Load a diffusers-format directory (config.json + diffusion_pytorch_model.{safetensors,bin})."""
-        root = os.path.join(path, subfolder) if subfolder else path
-        with open(os.path.join(root, cls.config_name)) as f:
-            model = cls.from_config(json.load(f), **overrides)
-        from ._ckpt import load_state
-        state = load_state(root, "diffusion_pytorch_model", variant)
-        model.load_state_dict(state)
-        return model.to(torch_dtype) if torch_dtype is not None else model
-
-    def save_pretrained(self, path):
-        os.makedirs(path, exist_ok=True)
-        cfg = dict(vars(self.config), _class_name="UNet3DConditionModel")
-        with open(os.path.join(path, self.config_name), "w") as f:
-            json.dump(cfg, f, indent=2)
-        from safetensors.torch import save_file
-        save_file({k: v.contiguous().cpu() for k, v in self.state_dict().items()},
-                  os.path.join(path, "diffusion_pytorch_model.safetensors"))
 
     # ------------------------------------------------------------------ hot path
     def _core(self, sample, cond, mask, t, motion_t, cond_emb, text_tokens, g: Grid, text_len: int, upsample_sizes, cfg_dup=False):
@@ -419,8 +334,7 @@ class UNet3DConditionModel(nn.Module):
         `cross_attention_kwargs`, `image_embeds` are accepted and unused, as in the reference."""
         if down_block_additional_residuals is not None or mid_block_additional_residual is not None:
             raise NotImplementedError("ControlNet residual hooks are not part of the MI355X hot path")
-        if not sample.is_cuda and not _lib.host_pointers_ok():
-            raise RuntimeError("animate_anything_amd.UNet3DConditionModel runs on the GPU only (no CPU fallback)")
+        self.require_device(sample)
         dt, dev = self.dtype, sample.device
         b, _, frames, h, w = sample.shape
         t = timestep
@@ -444,12 +358,7 @@ class UNet3DConditionModel(nn.Module):
         y = y.reshape(b, frames + 1, h, w, -1)[..., :self.conv_out.out_channels].permute(0, 4, 1, 2, 3)[:, :, 1:]       # :521-522 (columns past out_channels: _conv_out_pack)
         return UNet3DConditionOutput(sample=y) if return_dict else (y,)
 
-    # ------------------------------------------------------------------ sessions: static inputs (+ hipGraph replay)
-    def enable_graph(self, enabled=True):
-        """Capture the forward (timestep embedding + input packing + `_core`) in a hipGraph on first use per input
-        signature and replay it afterwards (removes ~1k host launches per denoising step)."""
-        self._graph = {} if enabled else None
-
+    # ------------------------------------------------------------------ opt-in paths
     def enable_fp8_feedforward(self, min_dim=None):
         """Opt in to the W8A8 (OCP e4m3) FeedForward path: every spatial and temporal transformer FeedForward with `dim >= min_dim` (default
         layers.FP8_FF_MIN_DIM = 640; the 320-channel ones keep their fused kernel) runs quantise -> GEGLU contraction -> quantise -> ff-out
@@ -488,6 +397,7 @@ class UNet3DConditionModel(nn.Module):
             blk.s1 = blk.s2 = blk.b1 = blk.b2 = None
         self.invalidate_caches()
 
+    # ------------------------------------------------------------------ sessions: static inputs (+ hipGraph replay)
     def session(self, batch, frames, h, w, text_shape, use_mask, has_motion, has_cond_emb, sample_dtype, sample_batch,
                 cond_batch, mask_batch, device, cfg_dup=False):
         """The static input buffers (and, when graphs are enabled, the captured hipGraph) of one input signature.
@@ -495,20 +405,15 @@ class UNet3DConditionModel(nn.Module):
         `sess.inputs[...]` once and then only calls `sess.run()` per step."""
         key = (batch, frames, h, w, tuple(text_shape), use_mask, has_motion, has_cond_emb, sample_dtype, sample_batch,
                cond_batch, mask_batch, self.dtype, str(device), bool(cfg_dup))
-        store = self._graph if self._graph is not None else self.__dict__.setdefault("_eager_sessions", {})
-        sess = store.get(key)
-        if sess is None:
-            if self._graph is None:
-                store.clear()                                  # eager sessions hold only input buffers: keep one
-            sess = store[key] = _Session(self, key, device)
-        return sess
+        return self._session(key, device, _Session)
 
 
-class _Session:
+class _Session(Session):
     def __init__(self, net, key, device):
+        super().__init__(net)
         (b, frames, h, w, text_shape, use_mask, has_motion, has_cond_emb, sample_dtype, sample_batch, cond_batch, mask_batch,
          dt, _dev, self.cfg_dup) = key
-        self.net, self.b, self.frames, self.h, self.w = net, b, frames, h, w
+        self.b, self.frames, self.h, self.w = b, frames, h, w
         z = lambda *s, dtype=dt: torch.zeros(*s, dtype=dtype, device=device)
         c = net.config.in_channels
         self.inputs = dict(sample=z(sample_batch, c, frames, h, w, dtype=sample_dtype), cond=z(cond_batch, c, 1, h, w),
@@ -528,32 +433,9 @@ class _Session:
             for i in range(net.num_upsamplers):
                 ups[i] = sizes[net.num_upsamplers - 1 - i]
         self.upsample_sizes = tuple(ups)
-        self.graph = None
-        self.out = None
-
-    def load(self, **tensors):
-        for k, v in tensors.items():
-            dst = self.inputs[k]
-            if dst is not None and v is not None and dst.data_ptr() != v.data_ptr():
-                dst.copy_(v.reshape(dst.shape) if v.numel() == dst.numel() else v.expand(dst.shape))
 
     def _core(self):
         i = self.inputs
         return self.net._core(i["sample"], i["cond"], i["mask"], i["t"], i["motion"], i["cond_emb"],
                               i["text"].reshape(-1, i["text"].shape[-1]), self.grid, self.text_len, self.upsample_sizes,
                               cfg_dup=self.cfg_dup)
-
-    def run(self):
-        if self.net._graph is None:
-            return self._core()
-        if self.graph is None:
-            s = torch.cuda.Stream()
-            s.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(s):                                   # warm-up outside capture (packs weights, autotunes)
-                self._core()
-            torch.cuda.current_stream().wait_stream(s)
-            self.graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self.graph):
-                self.out = self._core()
-        self.graph.replay()
-        return self.out

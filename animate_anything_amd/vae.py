@@ -11,14 +11,13 @@ no memory reason to slice on a 288 GB part).
 """
 from __future__ import annotations
 
-import json
-import os
 from types import SimpleNamespace
 
 import torch
 import torch.nn as nn
 
-from . import _lib, ops
+from . import ops
+from ._model import PretrainedModel
 from .layers import Conv2d, Downsample2D, Grid, GroupNorm, Linear, ResnetBlock2D, Upsample2D
 
 
@@ -174,8 +173,23 @@ def _to_tokens8(x):
     return t.reshape(-1, 8)
 
 
-class AutoencoderKL(nn.Module):
-    config_name = "config.json"
+class _KLEncoderModel(PretrainedModel):
+    """What AutoencoderKL and AutoencoderKLTemporalDecoder (svd_vae.py) share: `encoder` + `quant_conv` -> the latent distribution."""
+
+    def encode(self, x):
+        """x [N,3,H,W] in [-1,1] -> .latent_dist (DiagonalGaussianDistribution over [N,4,H/8,W/8])."""
+        self.require_device(x)
+        x = x.to(self.dtype)
+        n, _, h, w = x.shape
+        m, g = self.encoder.tokens(_to_tokens8(x), Grid(1, n, h, w))
+        m = self.quant_conv.tokens(m, ops.linear_geom(m.shape[0]))
+        moments = m.reshape(n, g.h, g.w, -1).permute(0, 3, 1, 2).contiguous()
+        return SimpleNamespace(latent_dist=DiagonalGaussianDistribution(moments))
+
+
+class AutoencoderKL(_KLEncoderModel):
+    class_name = "AutoencoderKL"
+    config_extra = {"_class_name": "AutoencoderKL"}
 
     def __init__(self, in_channels=3, out_channels=3, block_out_channels=(128, 256, 512, 512), layers_per_block=2,
                  latent_channels=4, norm_num_groups=32, scaling_factor=0.18215, force_upcast=True, **_):
@@ -192,59 +206,15 @@ class AutoencoderKL(nn.Module):
         self.post_quant_conv = Conv2d(latent_channels, latent_channels, 1)
         self.use_slicing = False
 
-    @property
-    def dtype(self):
-        return next(self.parameters()).dtype
-
-    @property
-    def device(self):
-        return next(self.parameters()).device
-
     def enable_slicing(self):
         self.use_slicing = True
 
     def disable_slicing(self):
         self.use_slicing = False
 
-    @classmethod
-    def from_pretrained(cls, path, subfolder=None, torch_dtype=None, variant=None, **overrides):
-        root = os.path.join(path, subfolder) if subfolder else path
-        with open(os.path.join(root, cls.config_name)) as f:
-            cfg = {k: v for k, v in json.load(f).items() if not k.startswith("_")}
-        cfg.update(overrides)
-        import inspect
-        ok = set(inspect.signature(cls.__init__).parameters) - {"self", "_"}
-        model = cls(**{k: v for k, v in cfg.items() if k in ok})
-        from ._ckpt import load_state
-        state = load_state(root, "diffusion_pytorch_model", variant)
-        model.load_state_dict(state)
-        return model.to(torch_dtype) if torch_dtype is not None else model
-
-    def save_pretrained(self, path):
-        os.makedirs(path, exist_ok=True)
-        with open(os.path.join(path, self.config_name), "w") as f:
-            json.dump(dict(vars(self.config), _class_name="AutoencoderKL"), f, indent=2)
-        from safetensors.torch import save_file
-        save_file({k: v.contiguous().cpu() for k, v in self.state_dict().items()},
-                  os.path.join(path, "diffusion_pytorch_model.safetensors"))
-
-    def _guard(self, x):
-        if not x.is_cuda and not _lib.host_pointers_ok():
-            raise RuntimeError("animate_anything_amd.AutoencoderKL runs on the GPU only (no CPU fallback)")
-
-    def encode(self, x):
-        """x [N,3,H,W] in [-1,1] -> .latent_dist (DiagonalGaussianDistribution over [N,4,H/8,W/8])."""
-        self._guard(x)
-        x = x.to(self.dtype)
-        n, _, h, w = x.shape
-        m, g = self.encoder.tokens(_to_tokens8(x), Grid(1, n, h, w))
-        m = self.quant_conv.tokens(m, ops.linear_geom(m.shape[0]))
-        moments = m.reshape(n, g.h, g.w, -1).permute(0, 3, 1, 2).contiguous()
-        return SimpleNamespace(latent_dist=DiagonalGaussianDistribution(moments))
-
     def decode(self, z):
         """z [N,4,h,w] -> .sample [N,3,8h,8w]."""
-        self._guard(z)
+        self.require_device(z)
         z = z.to(self.dtype)
         n, _, h, w = z.shape
         z8 = _to_tokens8(z)

@@ -53,6 +53,65 @@ def test_small_svd_unet_matches_oracle(dtype, text_len, pixel_major, monkeypatch
     assert torch.equal(replay[0], got) and torch.equal(replay[1], got)          # hipGraph replay == eager, bit for bit
 
 
+def test_small_svd_unet_graph_follows_load_state_dict():
+    """A captured hipGraph replays launches that point at the packed copies of the weights: `load_state_dict` drops the captured
+    sessions (_model.GraphModel.invalidate_caches), so the next run captures again and computes, bit for bit, what a fresh model
+    holding the new weights computes eagerly.  (tests/test_lora.py holds the UNet3D counterpart.)"""
+    ref, net = _pair(O.UNetSpatioTemporalConditionModel, UNetSpatioTemporalConditionModel, SMALL_SVD_UNET, torch.float16)
+    g = torch.Generator().manual_seed(9)
+    perturbed = {k: v + 0.02 * v.abs().mean() * torch.randn(v.shape, generator=g) for k, v in ref.state_dict().items()}
+    fresh = UNetSpatioTemporalConditionModel(**SMALL_SVD_UNET).eval()
+    fresh.load_state_dict(perturbed)
+    fresh = fresh.to("cuda", torch.float16)
+    i = svd_unet_inputs(2, 4, 16, 24, text_dim=128)
+    with torch.no_grad():
+        net.enable_graph()
+        first = [_run(net, i, torch.float16).clone() for _ in range(2)]              # capture, then replay
+        assert len(net._graph) == 1
+        net.load_state_dict(perturbed)
+        assert net._graph == {}
+        last = [_run(net, i, torch.float16).clone() for _ in range(2)]
+        want = _run(fresh, i, torch.float16)
+    assert torch.equal(first[0], first[1]) and torch.isfinite(want).all()
+    assert torch.equal(last[0], want) and torch.equal(last[1], want)
+    assert not torch.equal(last[1], first[0])
+
+
+def test_capture_keeps_the_cycle_collector_out():
+    """_model.Session.run: a dropped model is cyclic garbage (model <-> sessions) that owns hipGraphs and device memory; were it
+    released while another session captures, the process would abort.  The capture therefore starts with the garbage collected
+    and runs with the collector held off, and the collector is on again afterwards."""
+    import gc
+    import weakref
+    from animate_anything_amd._model import Session
+
+    class Net:
+        _graph = {}
+
+    class Dropped:
+        pass
+
+    class Counter(Session):
+        def __init__(self, net):
+            super().__init__(net)
+            self.x, self.seen = torch.zeros(4, device="cuda"), []
+
+        def _core(self):
+            self.seen.append((gc.isenabled(), dropped() is None))
+            return self.x.add_(1)
+
+    d = Dropped()
+    d.me = d
+    dropped = weakref.ref(d)
+    del d
+    sess = Counter(Net())
+    assert gc.isenabled()
+    out = sess.run()                                                    # warm-up (runs), capture (records), replay (runs)
+    assert len(sess.seen) == 2 and sess.seen[0][0] and sess.seen[1] == (False, True)
+    assert gc.isenabled() and torch.equal(out.cpu(), torch.full((4,), 2.0))
+    assert torch.equal(sess.run().cpu(), torch.full((4,), 3.0)) and len(sess.seen) == 2
+
+
 def test_full_architecture_svd_unet_matches_oracle():
     """The real 1.5 G-parameter architecture (320/640/1280/1280, heads 5/10/20/20, 9 input channels) on a small grid: every
     layer type at its real width, oracle live on the host."""
