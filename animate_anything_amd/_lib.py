@@ -219,6 +219,14 @@ class AaWindowMerge(C.Structure):
     ]
 
 
+class AaFreeInit(C.Structure):
+    _fields_ = [
+        ("x", C.c_void_p), ("n0", C.c_void_p), ("z", C.c_void_p), ("out", C.c_void_p), ("mask", C.c_void_p), ("twiddle", C.c_void_p),
+        ("volumes", C.c_int32), ("frames", C.c_int32), ("h", C.c_int32), ("w", C.c_int32),
+        ("a", C.c_float), ("s", C.c_float),
+    ]
+
+
 _I, _I32, _I64, _F, _V, _Z, _P = C.c_int, C.c_int32, C.c_int64, C.c_float, C.c_void_p, C.c_size_t, C.POINTER
 
 
@@ -274,6 +282,8 @@ PROTOTYPES = {
     "aa_cfg_rescale_tokens": (_I, [_P(AaCfgRescale), _V, _Z, _V]),
     "aa_window_gather_latents": _launch(AaWindowGather),
     "aa_window_merge_tokens": _launch(AaWindowMerge),
+    "aa_freeinit_workspace": (_Z, [_P(AaFreeInit)]),
+    "aa_freeinit_mix": (_I, [_P(AaFreeInit), _V, _Z, _V]),
 }
 SYMBOLS = tuple(PROTOTYPES)
 

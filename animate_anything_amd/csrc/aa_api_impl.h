@@ -23,6 +23,7 @@
 #include "kernels/freeu.h"
 #include "kernels/cfg_rescale.h"
 #include "kernels/window.h"
+#include "kernels/freeinit.h"
 
 namespace aa {
 
@@ -1253,6 +1254,50 @@ int aa_window_merge_tokens(const AaWindowMerge* d, void* stream) {
         else AA_LAUNCH((window_merge_kernel<T, false>), grid, block, 0, stream, *d);
     });
     return finish("window_merge_tokens");
+}
+
+static bool freeinit_geometry_ok(const AaFreeInit* d) {
+    if (d->volumes < 1 || d->frames < 1 || d->h < 1 || d->w < 1 || d->frames > aa::FI_MAX || d->h > aa::FI_MAX || d->w > aa::FI_MAX) return false;
+    return (int64_t)d->volumes * d->frames * d->h * d->w < ((int64_t)1 << 31);
+}
+
+size_t aa_freeinit_workspace(const AaFreeInit* d) {
+    if (!d || !freeinit_geometry_ok(d)) return 0;
+    return (size_t)d->volumes * d->frames * d->h * d->w * 2 * sizeof(float);
+}
+
+int aa_freeinit_mix(const AaFreeInit* d, void* workspace, size_t workspace_bytes, void* stream) {
+    using namespace aa;
+    if (!d || !d->x || !d->n0 || !d->z || !d->out || !d->mask || !d->twiddle) return fail(AA_E_SHAPE, "freeinit_mix: null operand");
+    if (!freeinit_geometry_ok(d))
+        return fail(AA_E_SHAPE, "freeinit_mix: bad geometry (volumes %d, frames %d, h %d, w %d; every axis 1 .. %d)", d->volumes, d->frames, d->h,
+                    d->w, FI_MAX);
+    if (!finite_f32(&d->a) || !finite_f32(&d->s)) return fail(AA_E_SHAPE, "freeinit_mix: a and s must be finite");
+    const size_t need = aa_freeinit_workspace(d);
+    if (!workspace || workspace_bytes < need) return fail(AA_E_WORKSPACE, "freeinit_mix: workspace %zu < %zu bytes", workspace_bytes, need);
+    if (!aligned_to(d->x, 4) || !aligned_to(d->n0, 4) || !aligned_to(d->z, 4) || !aligned_to(d->out, 4) || !aligned_to(d->mask, 4) ||
+        !aligned_to(d->twiddle, 8) || !aligned_to(workspace, 8))
+        return fail(AA_E_ALIGN, "freeinit_mix: x / n0 / z / out / mask must be 4-byte, the table and the workspace 8-byte aligned");
+    const int64_t vol = (int64_t)d->frames * d->h * d->w, n = vol * d->volumes;
+    const Span out = {d->out, n * 4}, ws = {workspace, (int64_t)need};
+    const Span in[5] = {{d->x, n * 4}, {d->n0, n * 4}, {d->z, n * 4}, {d->mask, vol * 4}, {d->twiddle, (int64_t)(d->frames + d->h + d->w) * 8}};
+    if (spans_overlap(out, in[0]) && d->out != d->x) return fail(AA_E_SHAPE, "freeinit_mix: out may be x itself or a separate buffer, not overlap it");
+    for (int i = 1; i < 5; ++i)
+        if (spans_overlap(out, in[i])) return fail(AA_E_SHAPE, "freeinit_mix: out must not overlap n0, z, the mask or the table");
+    if (spans_overlap(out, ws)) return fail(AA_E_SHAPE, "freeinit_mix: the workspace must not overlap out");
+    for (int i = 0; i < 5; ++i)
+        if (spans_overlap(ws, in[i])) return fail(AA_E_SHAPE, "freeinit_mix: the workspace must not overlap an operand");
+    f32x2* spec = (f32x2*)workspace;
+    const f32x2* tw = (const f32x2*)d->twiddle;
+    const dim3 block(FI_THREADS), rows((unsigned)fi_row_groups(*d));
+    AA_LAUNCH(freeinit_rows_fwd_kernel<>, rows, block, FI_ROWS_FWD_LDS, stream, *d, spec);
+    AA_LAUNCH((freeinit_axis_kernel<false>), dim3((unsigned)fi_axis_groups((int64_t)d->volumes * d->frames, d->w)), block, FI_AXIS_LDS, stream, spec,
+              tw + fi_tw_h(*d), d->h, d->w);
+    AA_LAUNCH(freeinit_frames_kernel<>, dim3((unsigned)fi_axis_groups(d->volumes, (int64_t)d->h * d->w)), block, FI_FRAMES_LDS, stream, *d, spec);
+    AA_LAUNCH((freeinit_axis_kernel<true>), dim3((unsigned)fi_axis_groups((int64_t)d->volumes * d->frames, d->w)), block, FI_AXIS_LDS, stream, spec,
+              tw + fi_tw_h(*d), d->h, d->w);
+    AA_LAUNCH(freeinit_rows_inv_kernel<>, rows, block, FI_ROWS_INV_LDS, stream, *d, (const f32x2*)spec);
+    return finish("freeinit_mix");
 }
 
 }  // extern "C"

@@ -8,7 +8,8 @@ num_frames,width,height,num_inference_steps,guidance_scale,fps}`, `seed`, `motio
 `sampler: ddim` for the checkpoint's own DDIM scheduler or `sampler: unipc` for UniPC (the sampler for 8-12 steps) in place
 of DPM-Solver++, `freeu: {s1: .., s2: .., b1: .., b2: ..}` for diffusers' FreeU switch and `validation_data.guidance_rescale`
 (a number in [0, 1], absent = 0) for diffusers' `guidance_rescale`, and `validation_data.context: {frames, overlap, weights,
-closed_loop}` for context windows - `num_frames` beyond the UNet's frame window.
+closed_loop}` for context windows - `num_frames` beyond the UNet's frame window - and `validation_data.free_init: {num_iters,
+use_fast_sampling, method, order, spatial_stop_frequency, temporal_stop_frequency}` for diffusers' FreeInit.
 The third-party pieces the reference pulls in and that do not exist in this image are replaced by small
 equivalents: OmegaConf -> PyYAML + dot-list merge, `VaeImageProcessor.preprocess` -> PIL lanczos resize + [-1,1]
 scaling, torchvision `ToTensor`/`Resize(antialias=False)` -> torch bilinear interpolate, imageio -> PIL GIF writer.
@@ -32,7 +33,7 @@ from PIL import Image
 
 from .pipeline import (DDPM_forward_timesteps, LatentToVideoPipeline, calculate_latent_motion_score,
                        check_context, tensor_to_vae_latent)
-from .schedulers import DDIMScheduler, DDPMScheduler, DPMSolverMultistepScheduler, UniPCMultistepScheduler
+from .schedulers import DDIMScheduler, DDPMScheduler, DPMSolverMultistepScheduler, UniPCMultistepScheduler, check_free_init
 from .unet3d import UNet3DConditionModel
 from .vae import AutoencoderKL
 
@@ -194,7 +195,8 @@ def eval(pipeline, validation_data, out_file, index, forward_t=25, preview=True,
             num_frames=validation_data.num_frames, num_inference_steps=validation_data.num_inference_steps,
             guidance_scale=validation_data.guidance_scale, condition_latent=input_image_latents, mask=mask,
             motion=[motion_strength], return_dict=False, timesteps=timesteps,
-            guidance_rescale=_check_guidance_rescale(validation_data), context=_check_context(validation_data), **prompt_kwargs)
+            guidance_rescale=_check_guidance_rescale(validation_data), context=_check_context(validation_data),
+            free_init=_check_free_init(validation_data), **prompt_kwargs)
     if preview:
         save_gif(out_file, video_frames, validation_data.get("fps", 8))
     real_motion_strength = calculate_latent_motion_score(video_latents.float()).cpu().numpy()[0]
@@ -241,6 +243,14 @@ def _check_context(validation_data):
     return check_context(dict(context) if isinstance(context, dict) else context)
 
 
+def _check_free_init(validation_data):
+    """`validation_data.free_init`: absent (None: off) or `{num_iters, use_fast_sampling, method, order, spatial_stop_frequency,
+    temporal_stop_frequency}` (schedulers.check_free_init: any key may be left out, an unknown one is refused); returns the completed
+    dict or None."""
+    free_init = validation_data.get("free_init") if validation_data is not None else None
+    return check_free_init(dict(free_init) if isinstance(free_init, dict) else free_init)
+
+
 def batch_eval(unet, text_encoder, vae, tokenizer, scheduler_config, validation_data, output_dir, preview,
                global_step=0, iters=6, generator=None, indices=None, seed=None, lora_path=None, lora_rank=16,
                unet_lora_modules=("UNet3DConditionModel",), guidance_group=None, sampler="dpm"):
@@ -252,6 +262,7 @@ def batch_eval(unet, text_encoder, vae, tokenizer, scheduler_config, validation_
     _check_sampler(sampler)
     _check_guidance_rescale(validation_data)
     _check_context(validation_data)
+    _check_free_init(validation_data)
     unet.eval()
     scheduler = SAMPLERS[sampler].from_config(scheduler_config)
     pipeline = LatentToVideoPipeline(vae=vae, text_encoder=text_encoder, tokenizer=tokenizer, unet=unet,
@@ -290,6 +301,7 @@ def main_eval(pretrained_model_path, validation_data, seed=None, motion_mask=Non
     freeu = _check_freeu(freeu)
     _check_guidance_rescale(validation_data)
     _check_context(validation_data)
+    _check_free_init(validation_data)
     from . import distributed as D
     rank, world, _dev = D.init()
     generator = None

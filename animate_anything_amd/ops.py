@@ -17,7 +17,7 @@ import torch
 
 from . import _lib
 from ._lib import (AA_ACT_GELU, AA_ACT_NONE, AA_ACT_QUICK_GELU, AA_ACT_SILU, AA_BF16, AA_F16, AA_F32, AaAttention, AaAttnOperand,
-                   AaBlend, AaConvGemm, AaFFFused, AaLinearRows, AaLinearFp8, AaQuantRowsFp8, AaDdimStepTok, AaDpmStep, AaDpmStepTok, AaEulerStepTok, AaGroupNorm, AaPackFrames, AaPackLatents, AaSeqSelfAttn, AaUnipcStepTok, AaFreeU, AaCfgRescale, AaWindow, AaWindowGather, AaWindowMerge)
+                   AaBlend, AaConvGemm, AaFFFused, AaLinearRows, AaLinearFp8, AaQuantRowsFp8, AaDdimStepTok, AaDpmStep, AaDpmStepTok, AaEulerStepTok, AaGroupNorm, AaPackFrames, AaPackLatents, AaSeqSelfAttn, AaUnipcStepTok, AaFreeU, AaCfgRescale, AaWindow, AaWindowGather, AaWindowMerge, AaFreeInit)
 
 _DT = {torch.float16: AA_F16, torch.bfloat16: AA_BF16, torch.float32: AA_F32}
 
@@ -1504,3 +1504,77 @@ def window_merge_tokens(tokens: torch.Tensor, acc: torch.Tensor, merged: torch.T
     d.window = w
     _run(lib.aa_window_merge_tokens, C.byref(d), _stream(acc))
     return merged
+
+
+# ------------------------------------------------------------------------------------- FreeInit
+_FREE_INIT_TABLES = {}
+_FREE_INIT_WS = {}
+
+
+class FreeInitTables:
+    """What aa_freeinit_mix reads besides the latents: `mask` fp32 [T, h, w] (unshifted, symmetrised) and `twiddle` fp32 [T + h + w, 2]."""
+
+    def __init__(self, mask, twiddle):
+        self.mask, self.twiddle = mask, twiddle
+        self.shape = tuple(mask.shape)
+
+
+def free_init_tables(T: int, h: int, w: int, mask: torch.Tensor, device) -> FreeInitTables:
+    """The tables of aa_freeinit_mix for a volume of T x h x w from the float64 low-pass `mask` in SHIFTED order
+    (schedulers.free_init_filter): the mask unshifted and symmetrised (schedulers.free_init_symmetric_mask) and the pairs
+    (cos 2 pi j / n, sin 2 pi j / n) for n = T, h, w in one array, both evaluated in float64 on the host and rounded once to fp32.
+    Cached per (T, h, w, device) and mask values."""
+    from .schedulers import free_init_symmetric_mask
+    T, h, w = int(T), int(h), int(w)
+    if tuple(mask.shape) != (T, h, w):
+        raise RuntimeError(f"free_init_tables: mask {tuple(mask.shape)} is not [T, h, w] = {(T, h, w)}")
+    mask = mask.detach().to(device="cpu", dtype=torch.float64)
+    key = (T, h, w, str(torch.device(device)))
+    kept = _FREE_INIT_TABLES.setdefault(key, [])
+    for m, tables in kept:
+        if torch.equal(m, mask):
+            return tables
+    tw = []
+    for n in (T, h, w):
+        ang = 2.0 * math.pi * torch.arange(n, dtype=torch.float64) / n
+        tw.append(torch.stack([torch.cos(ang), torch.sin(ang)], dim=1))
+    tables = FreeInitTables(free_init_symmetric_mask(mask).to(torch.float32).contiguous().to(device),
+                            torch.cat(tw).to(torch.float32).contiguous().to(device))
+    del kept[:-3]                                                 # (a handful of filters per shape at most)
+    kept.append((mask.clone(), tables))
+    return tables
+
+
+def freeinit_mix(x: torch.Tensor, n0: torch.Tensor, z: torch.Tensor, a: float, s: float, tables: FreeInitTables,
+                 out: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """FreeInit's re-initialisation out = z + LP(a * x + s * n0 - z) on fp32 latents [..., T, h, w] (aa_freeinit_mix: five launches,
+    direct DFTs per axis, LP the 3-d low-pass of `tables`): x the previous iteration's result, n0 the run's initial noise, z fresh
+    noise, a / s = sqrt(abar) / sqrt(1 - abar) at the last training timestep.  `out`: None (a new tensor) or a tensor of x's shape - x
+    itself is allowed, nothing else may overlap.  `workspace`: None (kept per device and geometry) or an fp32 tensor of at least
+    2 * x.numel() elements.  Returns `out`."""
+    lib = _lib.get()
+    if out is None:
+        out = torch.empty_like(x)
+    _check(x, n0, z, out, tables.mask, tables.twiddle, workspace)
+    T, h, w = tables.shape
+    for name, t in (("x", x), ("n0", n0), ("z", z), ("out", out)):
+        if t.dtype != torch.float32 or t.shape != x.shape or t.device != x.device:
+            raise RuntimeError(f"freeinit_mix: {name} must be fp32 of x's shape {tuple(x.shape)} on x's device")
+    if x.dim() < 3 or tuple(x.shape[-3:]) != (T, h, w) or x.numel() == 0:
+        raise RuntimeError(f"freeinit_mix: x {tuple(x.shape)} does not end in the tables' [T, h, w] = {(T, h, w)}")
+    if tables.mask.device != x.device:
+        raise RuntimeError(f"freeinit_mix: the tables are on {tables.mask.device}, x on {x.device}")
+    d = AaFreeInit()
+    d.x, d.n0, d.z, d.out, d.mask, d.twiddle = _ptr(x), _ptr(n0), _ptr(z), _ptr(out), _ptr(tables.mask), _ptr(tables.twiddle)
+    d.volumes, d.frames, d.h, d.w = x.numel() // (T * h * w), T, h, w
+    d.a, d.s = float(a), float(s)
+    if workspace is None:
+        nbytes = lib.aa_freeinit_workspace(C.byref(d))
+        key = (str(x.device), d.volumes, T, h, w)
+        workspace = _FREE_INIT_WS.get(key)
+        if workspace is None or workspace.numel() * 4 < nbytes:
+            workspace = _FREE_INIT_WS[key] = torch.empty(max(nbytes // 4, 2), dtype=torch.float32, device=x.device)
+    elif workspace.dtype != torch.float32 or workspace.device != x.device:
+        raise RuntimeError("freeinit_mix: the workspace must be fp32 on x's device")
+    _run(lib.aa_freeinit_mix, C.byref(d), _ptr(workspace), workspace.numel() * 4, _stream(x))
+    return out

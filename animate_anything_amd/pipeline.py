@@ -17,7 +17,8 @@ import torch
 
 from . import ops
 from ._model import PretrainedPipeline, read_scheduler_config
-from .schedulers import CONTEXT_WEIGHTS, DDIMScheduler, DPMSolverMultistepScheduler, UniPCMultistepScheduler, context_windows
+from .schedulers import (CONTEXT_WEIGHTS, DDIMScheduler, DPMSolverMultistepScheduler, UniPCMultistepScheduler, check_free_init,
+                         context_windows, free_init_filter, free_init_steps)
 
 
 class TextToVideoSDPipelineOutput(SimpleNamespace):
@@ -34,6 +35,16 @@ def _variance_noise(latents, generator):
     if gdev.type == dev.type:
         return torch.randn((b * f, c, h, w), generator=generator, device=dev, dtype=torch.float32)
     return torch.randn((b * f, c, h, w), generator=generator, device=gdev, dtype=torch.float32).to(dev)
+
+
+def _free_init_noise(latents, generator):
+    """The fresh noise of one FreeInit re-initialisation: fp32 in the latents' own shape (diffusers `randn_tensor(latents.shape)`), with
+    the generator-device handling of `_variance_noise`."""
+    dev = latents.device
+    gdev = generator.device if generator is not None else dev
+    if gdev.type == dev.type:
+        return torch.randn(tuple(latents.shape), generator=generator, device=dev, dtype=torch.float32)
+    return torch.randn(tuple(latents.shape), generator=generator, device=gdev, dtype=torch.float32).to(dev)
 
 
 def _latent_layout(flat, latents):
@@ -199,6 +210,33 @@ class LatentToVideoPipeline(PretrainedPipeline):
 
     def disable_freeu(self):
         self.unet.disable_freeu()
+
+    free_init = None             # the completed dict of check_free_init while FreeInit is enabled on the pipeline
+
+    def enable_free_init(self, num_iters=3, use_fast_sampling=False, method="butterworth", order=4, spatial_stop_frequency=0.25,
+                         temporal_stop_frequency=0.25):
+        """diffusers `FreeInitMixin.enable_free_init` (Wu et al., "FreeInit: Bridging Initialization Gap in Video Diffusion Models"):
+        every call samples `num_iters` times, each later iteration starting from the previous result re-noised to the last training
+        timestep, low-passed over (frames, h, w) and filled up with the high frequencies of fresh noise (`__call__`).  A per-call
+        `free_init=dict(...)` overrides what is set here."""
+        self.free_init = check_free_init(dict(num_iters=num_iters, use_fast_sampling=use_fast_sampling, method=method, order=order,
+                                              spatial_stop_frequency=spatial_stop_frequency, temporal_stop_frequency=temporal_stop_frequency))
+
+    def disable_free_init(self):
+        self.free_init = None
+
+    def free_init_scalars(self):
+        """(sqrt(abar), sqrt(1 - abar)) at the last training timestep: the re-noising `scheduler.add_noise(x, n0, N - 1)` of FreeInit."""
+        abar = float(self.scheduler.alphas_cumprod[self.scheduler.config.num_train_timesteps - 1])
+        return abar ** 0.5, (1.0 - abar) ** 0.5
+
+    @staticmethod
+    def free_init_tables(free_init, latents):
+        """The kernel tables (ops.free_init_tables) of the filter `free_init` describes, for the latents' whole [frames, h, w]."""
+        T, h, w = latents.shape[-3:]
+        mask = free_init_filter(T, h, w, free_init["method"], free_init["order"], free_init["spatial_stop_frequency"],
+                                free_init["temporal_stop_frequency"])
+        return ops.free_init_tables(T, h, w, mask, latents.device)
 
     # ------------------------------------------------------------------ helpers (diffusers TextToVideoSDPipeline)
     def check_inputs(self, prompt, height, width, callback_steps, negative_prompt=None, prompt_embeds=None,
@@ -423,21 +461,41 @@ class LatentToVideoPipeline(PretrainedPipeline):
                  guidance_scale=9.0, negative_prompt=None, eta=0.0, generator=None, latents=None,
                  prompt_embeds=None, negative_prompt_embeds=None, output_type="np", return_dict=True,
                  callback=None, callback_steps=1, cross_attention_kwargs=None, condition_latent=None,
-                 mask=None, timesteps=None, motion=None, guidance_rescale=0.0, context=None):
+                 mask=None, timesteps=None, motion=None, guidance_rescale=0.0, context=None, free_init=None):
+        """`free_init` (a mapping, check_free_init; None: what `enable_free_init` set, off by default) with num_iters > 1 - FreeInit:
+        the clip is sampled num_iters times.  Iteration 0 starts from the caller's latents n0; iteration i >= 1 from
+        ops.freeinit_mix(x, n0, z): the previous result x re-noised with n0 to the last training timestep, low-passed over the clip's
+        whole (frames, h, w), the high frequencies taken from z = one torch.randn of the latents' shape (fp32, the caller's generator).
+        `set_timesteps` runs before every iteration (a multistep scheduler's state starts afresh), under `use_fast_sampling` with
+        free_init_steps(...) steps - which a caller's own `timesteps` cannot follow: ValueError.  The mix sits outside `denoise`, so
+        guidance_rescale, context windows and FreeU compose with it unchanged.  DEPARTURE from diffusers: the latents stay fp32 between
+        iterations (diffusers rounds them to the model dtype).  num_iters = 1, or off: one `denoise`, no extra launch, no extra randn."""
         if latents is None:
             raise ValueError("LatentToVideoPipeline expects caller-prepared `latents` (reference pipeline.py:153)")
+        fi = check_free_init(free_init) if free_init is not None else self.free_init
+        iters = fi["num_iters"] if fi is not None else 1
+        fast = iters > 1 and fi["use_fast_sampling"]
+        if fast and timesteps is not None:
+            raise ValueError("free_init.use_fast_sampling shortens the schedule per iteration: it cannot be combined with `timesteps`")
         height = height or latents.shape[-2] * self.vae_scale_factor
         width = width or latents.shape[-1] * self.vae_scale_factor
         self.check_inputs(prompt, height, width, callback_steps, negative_prompt, prompt_embeds, negative_prompt_embeds)
         device = latents.device
         do_cfg = guidance_scale > 1.0
         prompt_embeds = self._encode_prompt(prompt, device, do_cfg, negative_prompt, prompt_embeds, negative_prompt_embeds)
-        self.scheduler.set_timesteps(num_inference_steps, device=device)
-        if timesteps is None:
-            timesteps = self.scheduler.timesteps
-        x = self.denoise(latents, prompt_embeds, condition_latent, mask, motion, [int(t) for t in timesteps],
-                         guidance_scale, callback, callback_steps, eta=eta, generator=generator, guidance_rescale=guidance_rescale,
-                         context=context)
+        x = latents
+        if iters > 1:
+            n0 = latents.to(torch.float32).contiguous()         # the run's initial noise, kept for every re-initialisation
+            a, s = self.free_init_scalars()
+            tables = self.free_init_tables(fi, latents)
+        for it in range(iters):
+            if it > 0:
+                x = ops.freeinit_mix(x, n0, _free_init_noise(n0, generator), a, s, tables, out=x)
+            self.scheduler.set_timesteps(free_init_steps(num_inference_steps, iters, it, fast), device=device)
+            ts = self.scheduler.timesteps if timesteps is None else timesteps
+            x = self.denoise(x, prompt_embeds, condition_latent, mask, motion, [int(t) for t in ts],
+                             guidance_scale, callback, callback_steps, eta=eta, generator=generator, guidance_rescale=guidance_rescale,
+                             context=context)
         latents = x.to(self.unet.dtype)
         if self.vae is None or output_type == "latent":
             video = None

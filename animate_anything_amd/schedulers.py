@@ -565,3 +565,79 @@ def context_windows(num_frames, length, overlap, closed_loop=False, weights="pyr
             holders[f].append(k)
     return [(idx, [float(np.float64(raw[j]) / total[f]) for j, f in enumerate(idx)],
              [holders[f][0] == k for f in idx], [holders[f][-1] == k for f in idx]) for k, idx in enumerate(frames)]
+
+
+# ------------------------------------------------------------------------------------- FreeInit
+FREE_INIT_METHODS = ("butterworth", "gaussian", "ideal")
+FREE_INIT_DEFAULTS = dict(num_iters=3, use_fast_sampling=False, method="butterworth", order=4, spatial_stop_frequency=0.25,
+                          temporal_stop_frequency=0.25)
+
+
+def check_free_init(free_init):
+    """The `free_init` argument (FreeInit, diffusers `enable_free_init`): None (off), or a mapping with the keys of FREE_INIT_DEFAULTS -
+    `num_iters` (an integer >= 1), `use_fast_sampling`, `method` ("butterworth" / "gaussian" / "ideal"), `order` (an integer >= 1; read
+    by butterworth), `spatial_stop_frequency` and `temporal_stop_frequency` (numbers >= 0) - any of them left out taking its default;
+    an unknown key or a value out of range raises ValueError.  Returns the completed dict, or None."""
+    if free_init is None:
+        return None
+    if not hasattr(free_init, "keys"):
+        raise ValueError(f"free_init {free_init!r}: a mapping with keys from {sorted(FREE_INIT_DEFAULTS)}")
+    unknown = sorted(set(free_init.keys()) - set(FREE_INIT_DEFAULTS))
+    if unknown:
+        raise ValueError(f"free_init: unknown key(s) {unknown} (known: {sorted(FREE_INIT_DEFAULTS)})")
+    c = dict(FREE_INIT_DEFAULTS)
+    c.update({k: free_init[k] for k in free_init.keys()})
+    for k in ("num_iters", "order"):
+        if isinstance(c[k], bool) or not isinstance(c[k], int) or c[k] < 1:
+            raise ValueError(f"free_init.{k} = {c[k]!r}: an integer >= 1")
+    if not isinstance(c["use_fast_sampling"], bool):
+        raise ValueError(f"free_init.use_fast_sampling = {c['use_fast_sampling']!r}: true or false")
+    if c["method"] not in FREE_INIT_METHODS:
+        raise ValueError(f"free_init.method = {c['method']!r}: one of {FREE_INIT_METHODS}")
+    for k in ("spatial_stop_frequency", "temporal_stop_frequency"):
+        v = c[k]
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not (0.0 <= v < math.inf):       # (NaN fails the comparison)
+            raise ValueError(f"free_init.{k} = {v!r}: a finite number >= 0")
+        c[k] = float(v)
+    return c
+
+
+def free_init_filter(frames, h, w, method="butterworth", order=4, spatial_stop_frequency=0.25, temporal_stop_frequency=0.25):
+    """The low-pass mask of FreeInit (diffusers `_get_free_init_freq_filter`) as float64 [frames, h, w] in SHIFTED index order (zero
+    frequency at [frames // 2, h // 2, w // 2]).  With ss / ts the spatial / temporal stop frequency and
+        d2 = ((ss / ts) (2 t / frames - 1))^2 + (2 y / h - 1)^2 + (2 x / w - 1)^2:
+    butterworth 1 / (1 + (d2 / ss^2)^order), gaussian exp(-d2 / (2 ss^2)), ideal 1 where d2 <= 2 ss else 0 (diffusers compares the SQUARED
+    distance with twice the stop frequency; restated as it is); all zeros when ss == 0 or ts == 0."""
+    if method not in FREE_INIT_METHODS:
+        raise ValueError(f"free_init_filter: method {method!r} is not one of {FREE_INIT_METHODS}")
+    frames, h, w = int(frames), int(h), int(w)
+    ss, ts = float(spatial_stop_frequency), float(temporal_stop_frequency)
+    if ss == 0.0 or ts == 0.0:
+        return torch.zeros((frames, h, w), dtype=torch.float64)
+    t = (ss / ts) * (2.0 * torch.arange(frames, dtype=torch.float64) / frames - 1.0)
+    y = 2.0 * torch.arange(h, dtype=torch.float64) / h - 1.0
+    x = 2.0 * torch.arange(w, dtype=torch.float64) / w - 1.0
+    d2 = (t * t)[:, None, None] + (y * y)[None, :, None] + (x * x)[None, None, :]
+    if method == "butterworth":
+        return 1.0 / (1.0 + (d2 / (ss * ss)) ** int(order))
+    if method == "gaussian":
+        return torch.exp(-d2 / (2.0 * ss * ss))
+    return (d2 <= 2.0 * ss).to(torch.float64)
+
+
+def free_init_symmetric_mask(mask):
+    """The mask the kernel multiplies the UNSHIFTED spectrum with: Ms[k] = (Mu[k] + Mu[-k]) / 2, Mu = ifftshift(mask), -k modulo the
+    size per axis (float64 in, float64 out).  Re IFFT3(Mu * FFT3 d) == IFFT3(Ms * FFT3 d) for real d: with an even axis Mu is symmetric
+    already; with an odd one it is not, diffusers drops the imaginary part, and the symmetrised mask is that real part exactly."""
+    dims = tuple(range(mask.dim()))
+    mu = torch.roll(mask.to(torch.float64), [-(n // 2) for n in mask.shape], dims)            # ifftshift
+    neg = torch.roll(torch.flip(mu, dims), [1] * mask.dim(), dims)                            # Mu[-k mod n]
+    return 0.5 * (mu + neg)
+
+
+def free_init_steps(num_inference_steps, num_iters, i, fast=False):
+    """Denoising steps of FreeInit iteration `i` of `num_iters`: all of them, or under `use_fast_sampling` (diffusers)
+    max(1, int(num_inference_steps / num_iters * (i + 1)))."""
+    if not fast:
+        return int(num_inference_steps)
+    return max(1, int(num_inference_steps / num_iters * (i + 1)))

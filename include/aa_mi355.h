@@ -774,6 +774,37 @@ typedef struct AaWindowMerge {
 int aa_window_gather_latents(const AaWindowGather* d, void* stream);
 int aa_window_merge_tokens(const AaWindowMerge* d, void* stream);
 
+/* aa_freeinit_mix: the re-initialisation of FreeInit (Wu et al., "FreeInit: Bridging Initialization Gap in Video Diffusion Models";
+ * diffusers `FreeInitMixin`) between two sampling iterations, per (clip, channel) volume of contiguous fp32 [frames][h][w]:
+ *   out = z + LP(a * x + s * n0 - z),   LP(d) = Re IFFT3(mask * FFT3 d)   over (frames, h, w)
+ * which is diffusers' Re IFFT3(shift^-1(shift(FFT3 z_t) M + shift(FFT3 z) (1 - M))) with z_t = a x + s n0 (x: the previous iteration's
+ * latents, n0: the run's initial noise, z: fresh noise, a = sqrt(abar), s = sqrt(1 - abar) at the last training timestep) when `mask`
+ * is M in UNSHIFTED order and symmetrised, mask[k] = (Mu[k] + Mu[-k]) / 2 with Mu = ifftshift(M) and -k modulo the size per axis
+ * (ops.free_init_tables; for an odd axis Mu is not symmetric and diffusers drops the imaginary part - the symmetrised mask
+ * reproduces that exactly).  `twiddle` holds the fp32 pairs (cos 2 pi j / n, sin 2 pi j / n), j = 0 .. n-1, for n = frames, then n = h,
+ * then n = w (frames + h + w pairs, evaluated in float64 and rounded once).  Every axis is a direct DFT from its table (indexed by
+ * j * k mod n): sizes 1 .. 128, powers of two or not.  fp32 throughout, every sum in one thread in the order j = 0 .. n-1, no atomics: a
+ * replay, a second call and the in-place form repeat the bits.  Five launches over the complex fp32 workspace
+ * (aa_freeinit_workspace(d) = 8 * volumes * frames * h * w bytes).  `out` may be `x` itself; nothing else may overlap.  mask == 0
+ * everywhere returns z bit for bit (signed zeros aside).
+ * Refused with nothing launched - AA_E_SHAPE: a null descriptor or operand; volumes < 1; frames, h or w outside 1 .. 128; 2^31 or more
+ * elements; a or s not finite; `out` overlapping n0, z, the mask, the table or the workspace, or x other than as the identical
+ * pointer; the workspace overlapping an operand.  AA_E_WORKSPACE: a null or too small workspace.  AA_E_ALIGN: x / n0 / z / out / mask
+ * not 4-byte, the table or the workspace not 8-byte aligned. */
+typedef struct AaFreeInit {
+    const float* x;           /* fp32 [volumes][frames][h][w] */
+    const float* n0;          /* fp32 [volumes][frames][h][w] */
+    const float* z;           /* fp32 [volumes][frames][h][w] */
+    float* out;               /* fp32 [volumes][frames][h][w]; may be x */
+    const float* mask;        /* fp32 [frames][h][w], unshifted and symmetrised */
+    const float* twiddle;     /* fp32 [frames + h + w][2] = (cos, sin) */
+    int32_t volumes, frames, h, w;
+    float a, s;
+} AaFreeInit;
+
+size_t aa_freeinit_workspace(const AaFreeInit* d);
+int aa_freeinit_mix(const AaFreeInit* d, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
