@@ -242,6 +242,8 @@ PROTOTYPES = {
     "aa_last_error": (C.c_char_p, []),
     "aa_conv_gemm_workspace": (_Z, [_P(AaConvGemm)]),
     "aa_conv_gemm": _launch(AaConvGemm),
+    "aa_conv_gemm_group": (_I, [_P(_P(AaConvGemm)), _I32, _V]),
+    "aa_conv_gemm_group_ok": (_I, [_P(_P(AaConvGemm)), _I32, _I32]),
     "aa_conv_gemm_launch_count": (_I, [_P(AaConvGemm)]),
     "aa_conv_gemm_tickets": (_I, [_P(AaConvGemm)]),
     "aa_conv_gemm_reduce_launches": (_I, [_P(AaConvGemm)]),

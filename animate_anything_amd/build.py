@@ -184,7 +184,7 @@ def audit_x_kernels(lib_path):
     for k, (_agpr, scratch, _vgpr, spills) in sorted(meta.items()):
         if ("ff_fused_kernel" in k and "ELi0EEE" in k or "linear_rows_kernel" in k or "linear_fp8_kernel" in k or "quant_rows_fp8_kernel" in k) and (scratch or spills):
             problems.append(f"{k}: scratch {scratch} bytes, {spills} VGPR spills in a hot kernel")
-    xk = {k: v for k, v in meta.items() if "conv_gemm_x_kernel" in k}
+    xk = {k: v for k, v in meta.items() if "conv_gemm_x_kernel" in k or "conv_gemm_x_group_kernel" in k}      # (the grouped launch runs the same body)
     if len(xk) < 16:                                        # 8 tiles x {fp16, bf16} at the very least
         problems.append(f"only {len(xk)} hand-scheduled kernels found")
     bodies, cur = {}, None
@@ -210,7 +210,7 @@ def audit_x_kernels(lib_path):
         bad = lambda what: problems.append(f"{name}: {what}")
         if scratch or spills:
             bad(f"scratch {scratch} bytes, {spills} VGPR spills")
-        m = re.search(r"x_kernelI\w+?Li(\d+)ELi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)E", name)
+        m = re.search(r"x_(?:group_)?kernelI\w+?Li(\d+)ELi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)E", name)
         if m is None or name not in bodies:                  # another mangling / template parameter list, or no disassembly: not auditable
             bad("cannot parse the kernel name" if m is None else "no disassembly found")
             continue

@@ -415,7 +415,59 @@ static bool cg_launch_cfg(int cfg, const AaConvGemm& d, int m_begin, int m_end, 
 #endif
 }
 
+// aa_conv_gemm_group: the grouped launch exists for the tiles its two call sites run on after tuning (Upsample2D's parity classes,
+// ResnetBlock2D's conv_shortcut + conv1: 192 x 320 at the 64 x 64 / 32 x 32 levels, 256 x 320 for the long-K 32 x 32 calls, 192 x 256 at
+// 16 x 16, 128 x 128 at 8 x 8) - every further tile is another instance of the whole instruction stream per storage type.  A tile
+// lives in the unit of its table entry.
+static bool cg_group_tile(int cfg) { return cfg == 39 || cfg == 46 || cfg == 47 || cfg == 49; }
+
+template <typename T, int BM, int BN, int WM, int WN, int BK, int DP3, int DP0, int DP1, int RING = (BK == 64 ? 2 : 4), int PER_CU = 1>
+static void cg_launch_x_group(const CgxGroup& g, int wgs, void* stream) {
+    AA_LAUNCH((conv_gemm_x_group_kernel<T, BM, BN, WM, WN, BK, DP3, DP0, DP1, RING, PER_CU>), dim3(wgs), dim3(64 * WM * WN), cgx_lds_bytes(BM, BN, BK, RING, WM, WN, PER_CU), stream, g);
+}
+
+template <typename T, int G>
+bool cg_launch_group_tu(int cfg, const CgxGroup& g, int wgs, void* stream) {
+#define AA_TILE(i, ...) case i: if constexpr (i % AA_TU_GROUPS == G) { __VA_ARGS__; return true; } else return false;
+    switch (cfg) {
+        AA_TILE(39, cg_launch_x_group<T, 256, 320, 2, 2, 64, 7, 6, 5>(g, wgs, stream))
+        AA_TILE(46, cg_launch_x_group<T, 192, 256, 2, 2, 64, 5, 5, 4>(g, wgs, stream))
+        AA_TILE(47, cg_launch_x_group<T, 128, 128, 2, 2, 64, 2, 2, 2, 2, 2>(g, wgs, stream))
+        AA_TILE(49, cg_launch_x_group<T, 192, 320, 2, 2, 64, 6, 5, 5>(g, wgs, stream))
+        default: return false;
+    }
+#undef AA_TILE
+}
+#if AA_TU_GROUPS > 1
+#define AA_X(g) extern template bool cg_launch_group_tu<f16_t, g>(int, const CgxGroup&, int, void*); \
+                extern template bool cg_launch_group_tu<bf16_t, g>(int, const CgxGroup&, int, void*);
+AA_X(0) AA_X(1) AA_X(2) AA_X(3) AA_X(4) AA_X(5) AA_X(6) AA_X(7)
+#undef AA_X
+#endif
+
+template <typename T>
+static bool cg_launch_group(int cfg, const CgxGroup& g, int wgs, void* stream) {
+#if AA_TU_GROUPS > 1
+    switch (cfg % AA_TU_GROUPS) {
+        case 0: return cg_launch_group_tu<T, 0>(cfg, g, wgs, stream);
+        case 1: return cg_launch_group_tu<T, 1>(cfg, g, wgs, stream);
+        case 2: return cg_launch_group_tu<T, 2>(cfg, g, wgs, stream);
+        case 3: return cg_launch_group_tu<T, 3>(cfg, g, wgs, stream);
+        case 4: return cg_launch_group_tu<T, 4>(cfg, g, wgs, stream);
+        case 5: return cg_launch_group_tu<T, 5>(cfg, g, wgs, stream);
+        case 6: return cg_launch_group_tu<T, 6>(cfg, g, wgs, stream);
+        default: return cg_launch_group_tu<T, 7>(cfg, g, wgs, stream);
+    }
+#else
+    return cg_launch_group_tu<T, 0>(cfg, g, wgs, stream);
+#endif
+}
+
 #ifdef AA_TU_TILES_ONLY             // (csrc/aa_tiles.hip stops here: the launchers of one group, nothing of the API)
+#if AA_TU_GROUPS > 1                // the unit's share of the grouped launchers (the single-call ones are instantiated by the unit's own file)
+template bool cg_launch_group_tu<f16_t, AA_TU_GROUP>(int, const CgxGroup&, int, void*);
+template bool cg_launch_group_tu<bf16_t, AA_TU_GROUP>(int, const CgxGroup&, int, void*);
+#endif
 }  // namespace aa
 #else
 static int cg_rows(const AaConvGemm& d) { return (int)((int64_t)d.n_img * d.h_out * d.w_out); }     // M of the contraction
@@ -705,7 +757,8 @@ int aa_conv_gemm_tile_flags(int idx) {
     return (c.slab ? 1 : 0) | (c.x ? 2 : 0) | (c.sched << 2);
 }
 
-int aa_conv_gemm(const AaConvGemm* d, void* stream) {
+// What aa_conv_gemm and aa_conv_gemm_group ask of one descriptor before anything is planned or launched.
+static int conv_gemm_check(const AaConvGemm* d) {
     using namespace aa;
     if (!d) return fail(AA_E_SHAPE, "conv_gemm: null descriptor");
     const int ctot = d->c0 + d->c1;
@@ -744,9 +797,98 @@ int aa_conv_gemm(const AaConvGemm* d, void* stream) {
     // aa_set_tile_override stays a preference ("every following call whose packed width it divides").
     if (d->tile >= 0 && !aa_conv_gemm_tile_ok(d, d->tile))
         return fail(AA_E_SHAPE, "conv_gemm: tile %d (AaConvGemm.tile) cannot carry out this call (aa_conv_gemm_tile_ok == 0)", d->tile);
-    int rc = AA_OK;
+    return AA_OK;
+}
+
+int aa_conv_gemm(const AaConvGemm* d, void* stream) {
+    using namespace aa;
+    int rc = conv_gemm_check(d);
+    if (rc != AA_OK) return rc;
     if (with_dtype16(d->dtype, [&](auto t) { rc = conv_gemm_t<typename decltype(t)::type>(*d, stream); })) return rc;
     return fail(AA_E_DTYPE, "conv_gemm: unsupported dtype %d", d->dtype);
+}
+
+// The grouped launch of calls[0 .. n) on tile `tile` (< 0: the group tile with the fewest residency rounds x tile work): the kernel
+// argument and the grid size, or why there is none.  Members go in by K steps, longest first (stable): the short tiles fill the tail.
+static const char* cg_group_plan(const AaConvGemm* const* calls, int n, int tile, aa::CgxGroup& g, int& wgs, int& cfg) {
+    using namespace aa;
+    if (!calls || n < 2 || n > CGX_GROUP_MAX) return "2 .. 4 members";
+    for (int i = 0; i < n; ++i) {
+        const AaConvGemm* d = calls[i];
+        if (!d) return "null member";
+        if (d->dtype != calls[0]->dtype || (d->dtype != AA_F16 && d->dtype != AA_BF16)) return "members of one 16-bit storage type";
+        if (!cg_dma_ok(*d) || !cg_x_ok(*d)) return "every member must be a call the hand-scheduled tiles carry out";
+        if (d->k_splits > 1 || d->tickets) return "no member splits along K";
+        if (d->row_stats || d->row_coef || d->ln_stats) return "no member emits row statistics or folds a LayerNorm";
+        if (d->debug & 8) return "no phase probe inside a group";
+        if (cg_rows(*d) <= 0) return "empty member";
+    }
+    cfg = -1;
+    double best = 0.0;
+    for (int t = 0; t < kNumCgCfgs; ++t) {
+        if (!cg_group_tile(t) || (tile >= 0 && t != tile)) continue;
+        const CgCfg& c = kCgCfgs[t];
+        bool fits = c.x != 0;
+        int64_t tiles = 0;
+        for (int i = 0; i < n && fits; ++i) {
+            fits = cg_tile_fits(*calls[i], t);
+            tiles += (int64_t)((cg_rows(*calls[i]) + c.bm - 1) / c.bm) * (calls[i]->n_pad / c.bn);
+        }
+        if (!fits) continue;
+        const int64_t slots = 256 * c.per_cu;
+        const double cost = (double)((tiles + slots - 1) / slots) * c.bm * c.bn * c.per_cu / c.rate;
+        if (cfg < 0 || cost < best) { cfg = t; best = cost; }
+    }
+    if (cfg < 0) return "no grouped tile carries out every member";
+    const CgCfg& c = kCgCfgs[cfg];
+    int order[CGX_GROUP_MAX];
+    for (int i = 0; i < n; ++i) {
+        int j = i;
+        for (; j > 0 && calls[order[j - 1]]->k_pad < calls[i]->k_pad; --j) order[j] = order[j - 1];
+        order[j] = i;
+    }
+    int64_t end = 0;
+    for (int i = 0; i < CGX_GROUP_MAX; ++i) {
+        if (i < n) {
+            const AaConvGemm& d = *calls[order[i]];
+            g.d[i] = d;
+            g.d[i].k_splits = 1;
+            g.d[i].workspace = nullptr;
+            g.d[i].workspace_bytes = 0;
+            g.M[i] = cg_rows(d);
+            g.tiles_n[i] = d.n_pad / c.bn;
+            end += ((int64_t)((g.M[i] + c.bm - 1) / c.bm) * g.tiles_n[i] + 7) / 8 * 8;
+        } else {
+            g.d[i] = AaConvGemm{};
+            g.M[i] = g.tiles_n[i] = 0;
+        }
+        if (end >= ((int64_t)1 << 31)) return "grid too large";
+        g.end[i] = (int32_t)end;
+    }
+    wgs = (int)end;
+    return nullptr;
+}
+
+int aa_conv_gemm_group_ok(const AaConvGemm* const* calls, int32_t n, int32_t tile) {
+    aa::CgxGroup g;
+    int wgs, cfg;
+    return (tile >= 0 && tile < aa::kNumCgCfgs && cg_group_plan(calls, n, tile, g, wgs, cfg) == nullptr) ? 1 : 0;
+}
+
+int aa_conv_gemm_group(const AaConvGemm* const* calls, int32_t n, void* stream) {
+    using namespace aa;
+    if (!calls || n < 2 || n > CGX_GROUP_MAX) return fail(AA_E_SHAPE, "conv_gemm_group: %d members (2 .. %d)", n, CGX_GROUP_MAX);
+    for (int i = 0; i < n; ++i) {
+        if (const int rc = conv_gemm_check(calls[i])) return rc;
+        if (calls[i]->tile != calls[0]->tile) return fail(AA_E_SHAPE, "conv_gemm_group: the members name different tiles (%d, %d)", calls[0]->tile, calls[i]->tile);
+    }
+    CgxGroup g;
+    int wgs = 0, cfg = -1;
+    if (const char* why = cg_group_plan(calls, n, calls[0]->tile, g, wgs, cfg)) return fail(AA_E_SHAPE, "conv_gemm_group: %s", why);
+    bool launched = false;
+    if (!with_dtype16(calls[0]->dtype, [&](auto t) { launched = cg_launch_group<typename decltype(t)::type>(cfg, g, wgs, stream); }) || !launched)
+        return fail(AA_E_SHAPE, "conv_gemm_group: tile %d has no grouped kernel", cfg);
+    return finish("conv_gemm_group");
 }
 
 size_t aa_groupnorm_workspace(const AaGroupNorm* d) {

@@ -65,8 +65,12 @@ __host__ __device__ constexpr bool cgx_ticket_ok(int bm, int bn, int wm, int wn,
 // other runs its epilogue - the VALU-heavy GEGLU epilogue is as long as a K = 320 loop).
 // LIN: the call is a plain linear layer / 1x1 convolution (one tap, stride 1, no padding): the per-row pixel arithmetic (two
 // integer divisions per fed row), the tap masks and the tap walk of the K position are compiled out of the setup.
-template <typename T, int BM, int BN, int WM, int WN, int BK, int DP3, int DP0, int DP1, int RING = (BK == 64 ? 2 : 4), int PER_CU = 1, bool LIN = false>
-__global__ void __launch_bounds__(64 * WM * WN, (PER_CU * WM * WN + 3) / 4) conv_gemm_x_kernel(const AaConvGemm p, const int M, const int tiles_n, const int m_begin, const int k_splits) {
+//
+// The body of one workgroup: tile `bid` of the `nwg` = tiles_m * tiles_n workgroups of call p (rows [m_begin, M)), K range `ky` of `k_splits`.
+// conv_gemm_x_kernel runs it with its own grid; conv_gemm_x_group_kernel with a member's share of a grid that several calls share.
+template <typename T, int BM, int BN, int WM, int WN, int BK, int DP3, int DP0, int DP1, int RING, int PER_CU, bool LIN>
+__device__ __forceinline__ void conv_gemm_x_body(const AaConvGemm& p, const int M, const int tiles_n, const int m_begin, const int nwg, const int bid,
+                                                 const int k_splits, const int ky) {
     constexpr int STAGES = RING;
     static_assert(BK == 64 ? RING == 2 : (RING == 3 || RING == 4), "ring depth");
     constexpr int NW = WM * WN;
@@ -100,7 +104,6 @@ __global__ void __launch_bounds__(64 * WM * WN, (PER_CU * WM * WN + 3) / 4) conv
     const int wave = wave_id();
     const int wm = wave / WN, wn = wave % WN;
 
-    const int nwg = gridDim.x, bid = blockIdx.x;
     const int q = nwg >> 3, r = nwg & 7;
     const int xcd = bid & 7, idx = bid >> 3;
     const int logical = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
@@ -129,11 +132,11 @@ __global__ void __launch_bounds__(64 * WM * WN, (PER_CU * WM * WN + 3) / 4) conv
     // first DMA piece (1), with the first stage landed (6), behind the K loop (2), at exit (5); 100 MHz wall clock at entry (7) and
     // exit (4); which CU ran it (3)
     auto stamp = [&](int slot) __attribute__((always_inline)) {
-        if ((p.debug & 8) && tid == 0) reinterpret_cast<long long*>(p.workspace)[(int64_t)blockIdx.x * 8 + slot] = clock_now();
+        if ((p.debug & 8) && tid == 0) reinterpret_cast<long long*>(p.workspace)[(int64_t)bid * 8 + slot] = clock_now();
     };
     auto stamp_wall = [&](int slot, int id_slot) __attribute__((always_inline)) {
         if ((p.debug & 8) && tid == 0) {
-            long long* w = reinterpret_cast<long long*>(p.workspace) + (int64_t)blockIdx.x * 8;
+            long long* w = reinterpret_cast<long long*>(p.workspace) + (int64_t)bid * 8;
             w[slot] = wall_now();
             if (id_slot >= 0) w[id_slot] = hw_id();
         }
@@ -143,7 +146,7 @@ __global__ void __launch_bounds__(64 * WM * WN, (PER_CU * WM * WN + 3) / 4) conv
     const int ctot = p.c0 + p.c1;
     const int nk_all = p.k_pad / BK;
     const int k_per = (nk_all + k_splits - 1) / k_splits;
-    const int kbase = blockIdx.y * k_per;
+    const int kbase = ky * k_per;
     const int nk = max(0, min(k_per, nk_all - kbase));
     // (convolutions behind a nearest-neighbour resize - Upsample2D - stay with conv_gemm_dma.h: aa_conv_gemm_tile_ok)
     const bool linear = LIN || (p.kh * p.kw == 1 && p.stride == 1 && p.pad_h == 0 && p.pad_w == 0);
@@ -511,7 +514,7 @@ __global__ void __launch_bounds__(64 * WM * WN, (PER_CU * WM * WN + 3) / 4) conv
     const int m_tile = m_begin + tile_m * BM;
     const int n_wave = tile_n * BN + wn * (BN / WN);
     if (k_splits > 1) {
-        float* ws = reinterpret_cast<float*>(p.workspace) + ((int64_t)blockIdx.y * (M - m_begin) - m_begin) * p.n_pad;
+        float* ws = reinterpret_cast<float*>(p.workspace) + ((int64_t)ky * (M - m_begin) - m_begin) * p.n_pad;
         static_for<MI>([&](auto i_) __attribute__((always_inline)) {
             constexpr int i = decltype(i_)::value;
             const int m = m_tile + wm * (BM / WM) + i * 32 + ec;
@@ -537,15 +540,15 @@ __global__ void __launch_bounds__(64 * WM * WN, (PER_CU * WM * WN + 3) / 4) conv
         __threadfence();
         __syncthreads();
         if (tid == 0) {
-            const int ticket = atomicAdd(p.tickets + blockIdx.x, 1);
+            const int ticket = atomicAdd(p.tickets + bid, 1);
             const int last = ticket == k_splits - 1;
-            if (last) p.tickets[blockIdx.x] = 0;
+            if (last) p.tickets[bid] = 0;
             *last_flag = last;
         }
         __syncthreads();
         if (*last_flag == 0) return;
         __threadfence();
-        const int my_split = blockIdx.y;
+        const int my_split = ky;
         const float* ws0 = reinterpret_cast<const float*>(p.workspace) - (int64_t)m_begin * p.n_pad;
         const int64_t split_stride = (int64_t)(M - m_begin) * p.n_pad;
         const BufRsrc r_cb = make_rsrc(p.bias, (p.bias && !p.bias_per_row) ? (unsigned)p.n_out * 2u : 0u);      // (per-row biases: general epilogue)
@@ -594,6 +597,37 @@ __global__ void __launch_bounds__(64 * WM * WN, (PER_CU * WM * WN + 3) / 4) conv
                               (p.row_stats || p.row_coef) ? tile_n * WN + wn : -1, ln_scale, (p.row_coef && tiles_n == 1) ? sCoef : nullptr, WN);
     stamp(5);
     stamp_wall(4, -1);
+}
+
+template <typename T, int BM, int BN, int WM, int WN, int BK, int DP3, int DP0, int DP1, int RING = (BK == 64 ? 2 : 4), int PER_CU = 1, bool LIN = false>
+__global__ void __launch_bounds__(64 * WM * WN, (PER_CU * WM * WN + 3) / 4) conv_gemm_x_kernel(const AaConvGemm p, const int M, const int tiles_n, const int m_begin, const int k_splits) {
+    conv_gemm_x_body<T, BM, BN, WM, WN, BK, DP3, DP0, DP1, RING, PER_CU, LIN>(p, M, tiles_n, m_begin, gridDim.x, blockIdx.x, k_splits, blockIdx.y);
+}
+
+// 2 .. CGX_GROUP_MAX independent calls in ONE launch (aa_conv_gemm_group): the kernel argument holds the members' descriptors by value
+// (no device-side table: a captured graph stays self-contained) and, per member, M, its column tiles and where its workgroup range ENDS.
+// Every range starts at a multiple of 8 workgroups, so a member's workgroups land on the XCDs a launch of its own would put them on and
+// the body sees the (nwg, bid) of that launch: same XCD ranges, same grouped tile order, same result bit for bit; the up to 7 workgroups
+// that pad a range return at once.  The host puts the member with the most K steps first: the short tiles fill the tail of the grid.
+// Members run whole (no m_begin, one K range) and through the general (non-LIN) instantiation: `linear` is a run-time flag there.
+constexpr int CGX_GROUP_MAX = 4;
+struct CgxGroup {
+    AaConvGemm d[CGX_GROUP_MAX];
+    int32_t M[CGX_GROUP_MAX], tiles_n[CGX_GROUP_MAX];
+    int32_t end[CGX_GROUP_MAX];          // first workgroup behind member i (a multiple of 8); unused members: the grid size
+};
+
+template <typename T, int BM, int BN, int WM, int WN, int BK, int DP3, int DP0, int DP1, int RING = (BK == 64 ? 2 : 4), int PER_CU = 1>
+__global__ void __launch_bounds__(64 * WM * WN, (PER_CU * WM * WN + 3) / 4) conv_gemm_x_group_kernel(const CgxGroup g) {
+    const int b = blockIdx.x;            // wave-uniform: the member and everything read through it stay in scalar registers
+    int mi = 0, begin = 0;
+#pragma unroll
+    for (int i = 1; i < CGX_GROUP_MAX; ++i)
+        if (b >= g.end[i - 1]) { mi = i; begin = g.end[i - 1]; }
+    const int M = g.M[mi], tiles_n = g.tiles_n[mi];
+    const int nwg = ((M + BM - 1) / BM) * tiles_n, bid = b - begin;
+    if (bid >= nwg) return;              // padding of the member's range
+    conv_gemm_x_body<T, BM, BN, WM, WN, BK, DP3, DP0, DP1, RING, PER_CU, false>(g.d[mi], M, tiles_n, 0, nwg, bid, 1, 0);
 }
 
 }  // namespace aa

@@ -251,14 +251,19 @@ class ResnetBlock2D(nn.Module):
             # [clips, Cout]: normally a column slice of ONE projection of all the blocks' time embeddings
             tproj = self.tproj if self.tproj is not None else self.time_emb_proj.tokens(temb_silu)
             self.tproj = None
-            h = self.conv1.tokens(h, geom, rowvec=tproj, rowvec_div=g.frames * g.hw)
+            conv1 = dict(x0=h, pw=self.conv1.packed(), g=geom, rowvec=tproj, rowvec_div=g.frames * g.hw)
         else:
-            h = self.conv1.tokens(h, geom)
+            conv1 = dict(x0=h, pw=self.conv1.packed(), g=geom)
+        # conv_shortcut reads the block input only: it rides in conv1's launch, where its short tiles fill the last round
+        # (ops.conv_gemm_group; None = not eligible, e.g. a conv1 that needs its K split: then the two launches as before)
+        shortcut = None if self.conv_shortcut is None else dict(x0=x, pw=self.conv_shortcut.packed(), g=ops.linear_geom(g.tokens), x1=x1)
+        outs = ops.conv_gemm_group([conv1, shortcut], unsplit_only=True) if shortcut is not None and ops.GROUP & 2 else None
+        h = ops.conv_gemm(**conv1) if outs is None else outs[0]
         h = self.norm2.tokens(h, g.images, g.hw, silu=True)
-        if self.conv_shortcut is not None:
-            skip = self.conv_shortcut.tokens(x, ops.linear_geom(g.tokens), x1=x1)
-        else:
+        if shortcut is None:
             skip = x
+        else:
+            skip = ops.conv_gemm(**shortcut) if outs is None else outs[1]
         return self.conv2.tokens(h, geom, residual=skip, out_scale=1.0 / self.output_scale_factor)
 
 
@@ -329,9 +334,12 @@ class Upsample2D(nn.Module):
         if up == (2 * g.h, 2 * g.w) and c % 64 == 0 and self.conv.out_channels % 8 == 0 and UPSAMPLE_AS_PARITY_CONVS:
             # exact x2: four 2x2 convolutions on the stored grid, each writing one output parity class (4/9 of the multiply-adds)
             out = torch.empty(g.images * up[0] * up[1], self.conv.out_channels, dtype=x.dtype, device=x.device)
-            for (a, b), pw in self.parity_packed().items():
-                geom = ops.Geom(g.images, g.h, g.w, g.h, g.w, 1, 1 - a, 1 - b)
-                ops.conv_gemm(x, pw, geom, out=out, out_map=(2, 2, a, b))
+            calls = [dict(x0=x, pw=pw, g=ops.Geom(g.images, g.h, g.w, g.h, g.w, 1, 1 - a, 1 - b), out=out, out_map=(2, 2, a, b))
+                     for (a, b), pw in self.parity_packed().items()]
+            # the classes read one input and write disjoint rows of one output: one launch for the four (ops.conv_gemm_group)
+            if not (ops.GROUP & 1) or ops.conv_gemm_group(calls) is None:
+                for kw in calls:
+                    ops.conv_gemm(**kw)
             return out, g.resized(*up)
         geom = ops.conv3x3_geom(g.images, g.h, g.w, up_to=up)
         return self.conv.tokens(x, geom), g.resized(*up)

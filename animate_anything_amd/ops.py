@@ -103,7 +103,8 @@ def save_tile_cache(path):
     """Persist the autotuned (tile, K splits) choices (json) so a later process can skip the tuning launches."""
     import json
     with open(path, "w") as f:
-        json.dump({"id": _tile_table_id(), "choices": [[list(k), list(v)] for k, v in sorted(_tile_cache.items())]}, f)
+        order = lambda kv: [(0, x, "") if isinstance(x, int) else (1, 0, str(x)) for x in kv[0]]      # (group signatures mix words and numbers)
+        json.dump({"id": _tile_table_id(), "choices": [[list(k), list(v)] for k, v in sorted(_tile_cache.items(), key=order)]}, f)
 
 
 def load_tile_cache(path):
@@ -575,6 +576,41 @@ def conv_gemm(x0: torch.Tensor, pw: PackedWeight, g: Geom, x1: Optional[torch.Te
                       None if residual is None else residual[i0 * ro:(i0 + n) * ro], act, out_dtype, out_scale, False,
                       out[i0 * ro * osc:(i0 + n) * ro * osc], bias, acc_scale, out_map, ls)
         return (out, None) if row_stats else out           # (chunks may run different tiles: no common statistics layout - the caller keeps its LayerNorm)
+    d, key, out, b = _conv_gemm_desc(x0, pw, g, x1, rowvec, rowvec_div, residual, act, out_dtype, out_scale, bias_per_row, out, bias,
+                                     acc_scale, out_map, ln_stats, row_stats)
+    _choose_tile(lib, d, key, g.rows, x0, (x0, x1, residual, rowvec), out)
+    ws = None
+    need = lib.aa_conv_gemm_workspace(C.byref(d))        # split-K scratch for few-tile / long-K calls
+    if DEBUG_ABLATE & 8:                                  # phase probe: [workgroup][8] shader-clock stamps
+        global LAST_STAMPS
+        ws = LAST_STAMPS = torch.zeros(2, 1 << 16, 8, dtype=torch.int64, device=x0.device)
+        d.workspace, d.workspace_bytes = _ptr(ws), ws.numel() * 8
+    elif need:
+        ws = torch.empty(need // 4, dtype=torch.float32, device=x0.device)
+        d.workspace, d.workspace_bytes = _ptr(ws), need
+    stats = None
+    if row_stats:                                         # after tile / workspace are settled: the plan decides whether it can emit them
+        parts = lib.aa_conv_gemm_row_stats_parts(C.byref(d))
+        if parts > 0 and coef_eps is not None and PRODUCER_COEF and lib.aa_conv_gemm_row_coef_ok(C.byref(d)):
+            coef = torch.empty(g.rows, 4, dtype=torch.float32, device=x0.device)       # the tile spans the row: finished coefficients
+            stats = RowStats(None, g.rows, 0, coef, (pw.n_out, float(coef_eps)))
+            d.row_coef, d.row_coef_eps = _ptr(coef), float(coef_eps)
+        elif parts > 0:
+            stats = RowStats(torch.empty(g.rows, parts, 2, dtype=torch.float32, device=x0.device), g.rows, parts)
+            d.row_stats, d.row_stats_parts = _ptr(stats.data), parts
+    _run(lib.aa_conv_gemm, C.byref(d), _stream(x0))
+    if TRACE is not None:
+        TRACE.append((d, (x0, x1, pw, b, rowvec, residual, out, ws, stats, ln_stats)))
+    return (out, stats) if row_stats else out
+
+
+def _conv_gemm_desc(x0, pw, g, x1=None, rowvec=None, rowvec_div=1, residual=None, act=AA_ACT_NONE, out_dtype=None, out_scale=1.0,
+                    bias_per_row=False, out=None, bias="packed", acc_scale=1.0, out_map=None, ln_stats=None, row_stats=False):
+    """The descriptor of one contraction (conv_gemm's arguments) with everything but the way it is carried out (tile, K split,
+    workspace, statistics outputs): -> (descriptor, tile-choice signature, out, bias).  Shared by conv_gemm and conv_gemm_group."""
+    b = pw.bias if isinstance(bias, str) else bias
+    c0 = x0.shape[-1]
+    c1 = 0 if x1 is None else x1.shape[-1]
     if c0 + c1 != pw.cin:
         raise RuntimeError(f"conv_gemm: activation has {c0}+{c1} channels, weight expects {pw.cin}")
     n_cols = pw.n_out // 2 if pw.geglu else pw.n_out
@@ -620,43 +656,143 @@ def conv_gemm(x0: torch.Tensor, pw: PackedWeight, g: Geom, x1: Optional[torch.Te
     d.tile, d.k_splits = -1, K_SPLITS
     key = (d.dtype, g.n_img, g.h_in, g.w_in, d.h_virt, d.w_virt, g.h_out, g.w_out, g.stride, pw.kh, pw.kw, c0, c1,
            pw.n_out, d.geglu, residual is not None) + (("ln",) if ln_stats is not None else ()) + (("stats",) if row_stats else ())
+    return d, key, out, b
+
+
+def _aliases(inputs, outs):
+    """Does an input share storage with an output (tuning launches write the outputs repeatedly: only safe when none does)."""
+    ptrs = {o.untyped_storage().data_ptr() for o in outs}
+    return any(t is not None and t.untyped_storage().data_ptr() in ptrs for t in inputs)
+
+
+def _choose_tile(lib, d, key, rows, x0, inputs, out):
+    """Settle (d.tile, d.k_splits) of one contraction: TILE_PICKER, else the tile cache / autotuner, else the library's own choice."""
+    d.tile, d.k_splits = -1, K_SPLITS
     if TILE_PICKER is not None and FORCE_TILE < 0 and K_SPLITS == 0:      # tile fuzzing (tests, scripts/debug): any eligible pair must be right
-        cands = _tile_candidates(d, g.rows)
+        cands = _tile_candidates(d, rows)
         d.tile, d.k_splits = TILE_PICKER(key, cands) if cands else (-1, 0)
     elif AUTOTUNE and x0.is_cuda and FORCE_TILE < 0 and K_SPLITS == 0:    # (explicit tile / split requests of tests and sweeps are not re-tuned)
         _load_default_tile_cache()
         choice = _tile_cache.get(key)
-        # the tuning launches write `out` repeatedly: only safe when no input of the call aliases it
-        aliased = any(t is not None and t.untyped_storage().data_ptr() == out.untyped_storage().data_ptr()
-                      for t in (x0, x1, residual, rowvec))
-        if choice is None and not aliased and not torch.cuda.is_current_stream_capturing():
-            choice = _autotune(lib, d, _stream(x0), key, g.rows, x0.device)
+        if choice is None and not _aliases(inputs, (out,)) and not torch.cuda.is_current_stream_capturing():
+            choice = _autotune(lib, d, _stream(x0), key, rows, x0.device)
         d.tile, d.k_splits = (-1, 0) if choice is None else choice
     if FORCE_TILE >= 0:                                   # tests / sweeps: THIS tile or an error (aa_conv_gemm rejects a tile that
         d.tile = FORCE_TILE                               # cannot carry out the call; the thread-local override merely prefers)
-    ws = None
-    need = lib.aa_conv_gemm_workspace(C.byref(d))        # split-K scratch for few-tile / long-K calls
-    if DEBUG_ABLATE & 8:                                  # phase probe: [workgroup][8] shader-clock stamps
-        global LAST_STAMPS
-        ws = LAST_STAMPS = torch.zeros(2, 1 << 16, 8, dtype=torch.int64, device=x0.device)
-        d.workspace, d.workspace_bytes = _ptr(ws), ws.numel() * 8
-    elif need:
-        ws = torch.empty(need // 4, dtype=torch.float32, device=x0.device)
-        d.workspace, d.workspace_bytes = _ptr(ws), need
-    stats = None
-    if row_stats:                                         # after tile / workspace are settled: the plan decides whether it can emit them
-        parts = lib.aa_conv_gemm_row_stats_parts(C.byref(d))
-        if parts > 0 and coef_eps is not None and PRODUCER_COEF and lib.aa_conv_gemm_row_coef_ok(C.byref(d)):
-            coef = torch.empty(g.rows, 4, dtype=torch.float32, device=x0.device)       # the tile spans the row: finished coefficients
-            stats = RowStats(None, g.rows, 0, coef, (pw.n_out, float(coef_eps)))
-            d.row_coef, d.row_coef_eps = _ptr(coef), float(coef_eps)
-        elif parts > 0:
-            stats = RowStats(torch.empty(g.rows, parts, 2, dtype=torch.float32, device=x0.device), g.rows, parts)
-            d.row_stats, d.row_stats_parts = _ptr(stats.data), parts
-    _run(lib.aa_conv_gemm, C.byref(d), _stream(x0))
-    if TRACE is not None:
-        TRACE.append((d, (x0, x1, pw, b, rowvec, residual, out, ws, stats, ln_stats)))
-    return (out, stats) if row_stats else out
+
+
+# Independent contractions issued back to back each pay a kernel boundary (ramp, partial last round: ~13 us per extra half-size kernel,
+# profiles/design_history_r05.md).  aa_conv_gemm_group runs 2..4 of them as ONE launch of one hand-scheduled tile.
+#   bit 0 (1): the four parity classes of Upsample2D - on: -0.30 ms of the step (12 launches + 4 leftover launches + 4 reduce launches -> 3);
+#   bit 1 (2): ResnetBlock2D's conv_shortcut next to conv1 - OFF: measured +0.13 ms on the step (the single conv1 keeps its split-off last
+#              round on a small tile, the group runs every row on the big one; profiles/r16_group_ab_same_box.txt, DESIGN.md section 8).
+# AA_GROUP=0 restores the separate launches everywhere, AA_GROUP=3 groups at both sites.
+GROUP = int(os.environ.get("AA_GROUP", "1"))
+if GROUP & ~3:
+    raise RuntimeError(f"AA_GROUP={GROUP}: only bits 0 (value 1, Upsample2D classes) and 1 (value 2, conv_shortcut + conv1) exist")
+GROUP_MAX = 4
+
+
+def _group_key(keys):
+    """The tile-choice signature of a group: its members' signatures in call order, flat (the tile cache stores flat keys)."""
+    out = ("group", len(keys))
+    for k in keys:
+        out += ("|",) + tuple(k)
+    return out
+
+
+def _autotune_group(lib, arr, n, ds, cands, stream, key):
+    """The fastest of `cands` (tiles every member accepts) for this group, timed like _autotune: one launch per measurement."""
+    global AUTOTUNE_EVENTS
+    AUTOTUNE_EVENTS += 1
+    best = cands[0]
+    if len(cands) > 1:
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+
+        def timed(c, reps):
+            for d in ds:
+                d.tile = c[0]
+            if lib.aa_conv_gemm_group(arr, n, stream) != 0:
+                return []
+            ts = []
+            for _ in range(reps):
+                e0.record()
+                lib.aa_conv_gemm_group(arr, n, stream)
+                e1.record()
+                e1.synchronize()
+                ts.append(e0.elapsed_time(e1))
+            return ts
+
+        samples = {c: [] for c in cands}
+        for _ in range(3):                                # interleaved passes (clock / power drift must not favour one candidate)
+            for c in cands:
+                samples[c] += timed(c, 7)
+        final = sorted((sorted(v)[len(v) // 2], c) for c, v in samples.items() if v)
+        if final:
+            best = final[0][1]
+    _tile_cache[key] = best
+    return best
+
+
+def conv_gemm_group(calls, unsplit_only=False):
+    """2..4 independent contractions as ONE kernel launch (aa_conv_gemm_group): `calls` = dicts of conv_gemm's arguments (x0, pw, g and
+    keywords; no ln_stats / row_stats / out_dtype).  No member may read another member's output.  Every member runs on one tile, chosen
+    per group signature (TILE_PICKER, tile cache, autotuner) among the tiles the library offers for this group, with one K range.
+    Returns the list of outputs - or None, with nothing launched, when the library offers no tile for the group (the caller then
+    issues the calls one by one).  `unsplit_only`: also None when a member on its own would run with a K split (a long-K member
+    that needs the split to fill the chip loses more inside a group than the launch saves)."""
+    lib = _lib.get()
+    n = len(calls)
+    if not 2 <= n <= GROUP_MAX:
+        raise RuntimeError(f"conv_gemm_group: {n} calls (2..{GROUP_MAX})")
+    ms = []
+    for kw in calls:
+        kw = dict(kw)
+        x0, pw, g = kw.pop("x0"), kw.pop("pw"), kw.pop("g")
+        if kw.get("ln_stats") is not None or kw.get("row_stats") or kw.get("out_dtype") is not None:
+            raise RuntimeError("conv_gemm_group: members carry no folded LayerNorm, row statistics or output dtype of their own")
+        osc = 1 if kw.get("out_map") is None else kw["out_map"][0] * kw["out_map"][1]
+        if kw.get("out_map") is not None and (kw.get("out") is None or kw["out"].shape[0] != g.rows * osc):
+            raise RuntimeError("conv_gemm_group: out_map needs `out` = the whole [n_img * h_out * sy * w_out * sx, N] grid")
+        _check(x0, kw.get("x1"), pw.w, kw.get("residual"), kw.get("out"))
+        d, key, out, b = _conv_gemm_desc(x0, pw, g, **kw)
+        ms.append((d, key, out, (x0, kw.get("x1"), pw, b, kw.get("rowvec"), kw.get("residual"), out, None, None, None), g.rows))
+    ds = [m[0] for m in ms]
+    x0 = calls[0]["x0"]
+    if unsplit_only:
+        for (d, key, out, keep, rows) in ms:
+            _choose_tile(lib, d, key, rows, x0, (keep[0], keep[1], keep[5], keep[4]), out)
+            if d.k_splits > 1 or lib.aa_conv_gemm_workspace(C.byref(d)):
+                return None
+    for d in ds:
+        d.tile, d.k_splits, d.tickets, d.tickets_len = -1, 1, None, 0
+    arr = (C.POINTER(AaConvGemm) * n)(*[C.pointer(d) for d in ds])
+    cands = [(i, 0) for i in range(len(TILE_TABLE)) if lib.aa_conv_gemm_group_ok(arr, n, i)]
+    if FORCE_TILE >= 0:
+        cands = [c for c in cands if c[0] == FORCE_TILE]
+    if not cands:
+        return None
+    key = _group_key([m[1] for m in ms])
+    choice = cands[0]
+    if TILE_PICKER is not None and FORCE_TILE < 0:
+        choice = TILE_PICKER(key, cands)
+    elif AUTOTUNE and x0.is_cuda and FORCE_TILE < 0:
+        _load_default_tile_cache()
+        choice = _tile_cache.get(key)
+        if choice is not None and tuple(choice) not in cands:
+            choice = None
+        inputs = [t for m in ms for t in (m[3][0], m[3][1], m[3][4], m[3][5])]
+        if choice is None and not _aliases(inputs, [m[2] for m in ms]) and not torch.cuda.is_current_stream_capturing():
+            choice = _autotune_group(lib, arr, n, ds, cands, _stream(x0), key)
+        if choice is None:
+            choice = cands[0]
+    for d in ds:
+        d.tile = choice[0]
+    _run(lib.aa_conv_gemm_group, arr, n, _stream(x0))
+    if TRACE is not None:                                 # every member on its own: the roofline / launch-list accounting sees contractions
+        for m in ms:
+            TRACE.append((m[0], m[3]))
+    return [m[2] for m in ms]
 
 
 # ------------------------------------------------------------------------------------- norms

@@ -140,6 +140,15 @@ typedef struct AaConvGemm {
  * (few output tiles, long K: the small-M levels); 0 when it would not. */
 size_t aa_conv_gemm_workspace(const AaConvGemm* d);
 int aa_conv_gemm(const AaConvGemm* d, void* stream);
+/* (added under version 110: no existing descriptor or entry point changed, so AA_VERSION stays.)  2 .. 4 INDEPENDENT contractions (no member reads another member's output - the caller's guarantee) as ONE kernel
+ * launch of one hand-scheduled tile: a kernel boundary (ramp, partial last residency round) is paid once instead of per call, and
+ * short-K members fill the last round of a long-K one.  Every member is computed exactly as aa_conv_gemm computes it on that tile
+ * with one K range (bit-identical output).  All members carry the same `tile` (>= 0: that tile; -1: the library picks) and one
+ * storage dtype; none splits along K (k_splits <= 1; workspace is ignored), uses `tickets`, `row_stats`, `row_coef`, `ln_stats` or
+ * the phase-probe debug bit.  Anything else: AA_E_SHAPE, nothing launched.  The launch carries the descriptors by value (a captured
+ * graph keeps no pointer to them).  aa_conv_gemm_group_ok: 1 iff aa_conv_gemm_group would launch these calls on tile `tile`. */
+int aa_conv_gemm_group(const AaConvGemm* const* calls, int32_t n, void* stream);
+int aa_conv_gemm_group_ok(const AaConvGemm* const* calls, int32_t n, int32_t tile);
 /* Number of kernel launches aa_conv_gemm makes for this descriptor (version 103): 1, plus a launch for a split-off last
  * round of tiles, plus split-K reduce launches - what a profiler counts per call (bench.py `roofline.kernel_launches_per_step`). */
 int aa_conv_gemm_launch_count(const AaConvGemm* d);
