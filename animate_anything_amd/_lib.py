@@ -227,6 +227,16 @@ class AaFreeInit(C.Structure):
     ]
 
 
+class AaKeepBlend(C.Structure):
+    _fields_ = [
+        ("x", C.c_void_p), ("out", C.c_void_p), ("known", C.c_void_p), ("mask", C.c_void_p), ("noise", C.c_void_p),
+        ("clips", C.c_int32), ("channels", C.c_int32), ("frames", C.c_int32), ("hw", C.c_int32),
+        ("known_clips", C.c_int32), ("known_frames", C.c_int32), ("mask_clips", C.c_int32), ("mask_frames", C.c_int32),
+        ("known_dtype", C.c_int32), ("mask_dtype", C.c_int32),
+        ("a", C.c_float), ("s", C.c_float),
+    ]
+
+
 _I, _I32, _I64, _F, _V, _Z, _P = C.c_int, C.c_int32, C.c_int64, C.c_float, C.c_void_p, C.c_size_t, C.POINTER
 
 
@@ -286,6 +296,7 @@ PROTOTYPES = {
     "aa_window_merge_tokens": _launch(AaWindowMerge),
     "aa_freeinit_workspace": (_Z, [_P(AaFreeInit)]),
     "aa_freeinit_mix": (_I, [_P(AaFreeInit), _V, _Z, _V]),
+    "aa_keep_blend": _launch(AaKeepBlend),
 }
 SYMBOLS = tuple(PROTOTYPES)
 

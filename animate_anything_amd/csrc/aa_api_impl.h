@@ -24,6 +24,7 @@
 #include "kernels/cfg_rescale.h"
 #include "kernels/window.h"
 #include "kernels/freeinit.h"
+#include "kernels/keep.h"
 
 namespace aa {
 
@@ -54,6 +55,12 @@ static bool with_dtype16(int dtype, F&& f) {
     if (dtype == AA_F16) { f(DType16<f16_t>{}); return true; }
     if (dtype == AA_BF16) { f(DType16<bf16_t>{}); return true; }
     return false;
+}
+// The same with fp32 as a third type (tag ::type float): operands that are stored in any of the three (aa_keep_blend's known / mask).
+template <typename F>
+static bool with_dtype(int dtype, F&& f) {
+    if (dtype == AA_F32) { f(DType16<float>{}); return true; }
+    return with_dtype16(dtype, f);
 }
 
 // What the four token step entry points share: the geometry test (`ld`: row pitch of the token matrix) and the launch grid.
@@ -1440,6 +1447,44 @@ int aa_freeinit_mix(const AaFreeInit* d, void* workspace, size_t workspace_bytes
               tw + fi_tw_h(*d), d->h, d->w);
     AA_LAUNCH(freeinit_rows_inv_kernel<>, rows, block, FI_ROWS_INV_LDS, stream, *d, (const f32x2*)spec);
     return finish("freeinit_mix");
+}
+
+int aa_keep_blend(const AaKeepBlend* d, void* stream) {
+    using namespace aa;
+    if (!d || !d->x || !d->out || !d->known || !d->mask) return fail(AA_E_SHAPE, "keep_blend: null operand");
+    if (d->clips < 1 || d->channels < 1 || d->frames < 1 || d->hw < 1 || (int64_t)d->clips * d->channels > 65535 || d->frames > 65535 ||
+        (int64_t)d->clips * d->channels * d->frames * d->hw >= ((int64_t)1 << 31))
+        return fail(AA_E_SHAPE, "keep_blend: bad geometry (clips %d, channels %d, frames %d, hw %d)", d->clips, d->channels, d->frames, d->hw);
+    if ((d->known_clips != 1 && d->known_clips != d->clips) || (d->known_frames != 1 && d->known_frames != d->frames) ||
+        (d->mask_clips != 1 && d->mask_clips != d->clips) || (d->mask_frames != 1 && d->mask_frames != d->frames))
+        return fail(AA_E_SHAPE, "keep_blend: known [%d clips, %d frames] / mask [%d clips, %d frames] must have 1 or all of %d clips, %d frames",
+                    d->known_clips, d->known_frames, d->mask_clips, d->mask_frames, d->clips, d->frames);
+    if (!finite_f32(&d->a) || !finite_f32(&d->s)) return fail(AA_E_SHAPE, "keep_blend: a and s must be finite");
+    if (!d->noise && d->s != 0.0f) return fail(AA_E_SHAPE, "keep_blend: s != 0 needs the noise operand");
+    const auto esize = [](int dtype) { return dtype == AA_F32 ? 4 : dtype == AA_F16 || dtype == AA_BF16 ? 2 : 0; };
+    const int ks = esize(d->known_dtype), ms = esize(d->mask_dtype);
+    if (!ks || !ms) return fail(AA_E_DTYPE, "keep_blend: unsupported dtype (known %d, mask %d)", d->known_dtype, d->mask_dtype);
+    if (!aligned_to(d->x, 4) || !aligned_to(d->out, 4) || !aligned_to(d->noise, 4) || !aligned_to(d->known, ks) || !aligned_to(d->mask, ms))
+        return fail(AA_E_ALIGN, "keep_blend: x / out / noise must be 4-byte aligned, known / mask aligned to their element size");
+    const int64_t planes = (int64_t)d->clips * d->channels, n = planes * d->frames * d->hw;
+    const Span out = {d->out, n * 4};
+    const Span in[3] = {{d->known, (int64_t)d->known_clips * d->channels * d->known_frames * d->hw * ks},
+                        {d->mask, (int64_t)d->mask_clips * d->mask_frames * d->hw * ms}, {d->noise, n * 4}};
+    if (d->out != d->x && spans_overlap(out, {d->x, n * 4})) return fail(AA_E_SHAPE, "keep_blend: out may be x itself or a separate buffer, not overlap it");
+    for (int i = 0; i < 3; ++i)
+        if (spans_overlap(out, in[i])) return fail(AA_E_SHAPE, "keep_blend: out must not overlap known, mask or noise");
+    const bool vec = d->hw % 4 == 0 && aligned16(d->x) && aligned16(d->out) && aligned16(d->known) && aligned16(d->mask) && aligned16(d->noise);
+    const int per_row = vec ? d->hw / 4 : d->hw;
+    const dim3 grid((unsigned)((per_row + KEEP_THREADS - 1) / KEEP_THREADS), (unsigned)d->frames, (unsigned)planes), block(KEEP_THREADS);
+    with_dtype(d->known_dtype, [&](auto kt) {
+        with_dtype(d->mask_dtype, [&](auto mt) {
+            using K = typename decltype(kt)::type;
+            using M = typename decltype(mt)::type;
+            if (vec) AA_LAUNCH((keep_blend_kernel<K, M, true>), grid, block, 0, stream, *d);
+            else AA_LAUNCH((keep_blend_kernel<K, M, false>), grid, block, 0, stream, *d);
+        });
+    });
+    return finish("keep_blend");
 }
 
 }  // extern "C"

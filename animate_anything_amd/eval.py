@@ -172,8 +172,8 @@ def eval(pipeline, validation_data, out_file, index, forward_t=25, preview=True,
     scale = math.sqrt(width * height / (validation_data.height * validation_data.width))
     validation_data.height = round(height / scale / 8) * 8
     validation_data.width = round(width / scale / 8) * 8
-    input_image = preprocess_image(pimg, validation_data.height, validation_data.width)
-    input_image = input_image.unsqueeze(0).to(dtype).to(device)
+    image = preprocess_image(pimg, validation_data.height, validation_data.width)        # fp32 [1, 3, H, W] in [-1, 1]
+    input_image = image.unsqueeze(0).to(dtype).to(device)
     input_image_latents = tensor_to_vae_latent(input_image, vae)
 
     np_mask = load_motion_mask(validation_data.mask if "mask" in validation_data else None, validation_data.width, validation_data.height)
@@ -189,6 +189,9 @@ def eval(pipeline, validation_data, out_file, index, forward_t=25, preview=True,
         emb = torch.load(validation_data.prompt_embeds, map_location=device)
         prompt_kwargs = dict(prompt_embeds=emb["prompt_embeds"].to(dtype),
                              negative_prompt_embeds=emb["negative_prompt_embeds"].to(dtype))
+    # keep_unmasked: what the mask holds still stays on the input image - the known-region blend on `condition_latent` under the latent
+    # `mask` behind every solver step, and the image's own pixels pasted back under the pixel mask after decoding
+    keep = dict(image=image, image_mask=np_mask / 255) if _check_keep_unmasked(validation_data) else None
     with torch.no_grad():
         video_frames, video_latents = pipeline(
             latents=initial_latents, width=validation_data.width, height=validation_data.height,
@@ -196,7 +199,7 @@ def eval(pipeline, validation_data, out_file, index, forward_t=25, preview=True,
             guidance_scale=validation_data.guidance_scale, condition_latent=input_image_latents, mask=mask,
             motion=[motion_strength], return_dict=False, timesteps=timesteps,
             guidance_rescale=_check_guidance_rescale(validation_data), context=_check_context(validation_data),
-            free_init=_check_free_init(validation_data), **prompt_kwargs)
+            free_init=_check_free_init(validation_data), keep=keep, **prompt_kwargs)
     if preview:
         save_gif(out_file, video_frames, validation_data.get("fps", 8))
     real_motion_strength = calculate_latent_motion_score(video_latents.float()).cpu().numpy()[0]
@@ -251,6 +254,19 @@ def _check_free_init(validation_data):
     return check_free_init(dict(free_init) if isinstance(free_init, dict) else free_init)
 
 
+def _check_keep_unmasked(validation_data, sampler=None):
+    """`validation_data.keep_unmasked`: absent (false) or a boolean - true: the region the motion mask holds still is kept on the input
+    image while sampling (pipeline `keep`).  Not with `sampler: unipc`, whose corrector never reads the sample it is handed
+    (pipeline._keep_setup).  Returns the boolean."""
+    on = validation_data.get("keep_unmasked", False) if validation_data is not None else False
+    if not isinstance(on, bool):
+        raise ValueError(f"validation_data.keep_unmasked = {on!r}: true or false")
+    if on and sampler == "unipc":
+        raise ValueError("validation_data.keep_unmasked: not available with sampler unipc (its corrector rebuilds the sample from its own "
+                         "state and would drop the blend); use dpm or ddim")
+    return on
+
+
 def batch_eval(unet, text_encoder, vae, tokenizer, scheduler_config, validation_data, output_dir, preview,
                global_step=0, iters=6, generator=None, indices=None, seed=None, lora_path=None, lora_rank=16,
                unet_lora_modules=("UNet3DConditionModel",), guidance_group=None, sampler="dpm"):
@@ -263,6 +279,7 @@ def batch_eval(unet, text_encoder, vae, tokenizer, scheduler_config, validation_
     _check_guidance_rescale(validation_data)
     _check_context(validation_data)
     _check_free_init(validation_data)
+    _check_keep_unmasked(validation_data, sampler)
     unet.eval()
     scheduler = SAMPLERS[sampler].from_config(scheduler_config)
     pipeline = LatentToVideoPipeline(vae=vae, text_encoder=text_encoder, tokenizer=tokenizer, unet=unet,
@@ -302,6 +319,7 @@ def main_eval(pretrained_model_path, validation_data, seed=None, motion_mask=Non
     _check_guidance_rescale(validation_data)
     _check_context(validation_data)
     _check_free_init(validation_data)
+    _check_keep_unmasked(validation_data, sampler)
     from . import distributed as D
     rank, world, _dev = D.init()
     generator = None

@@ -17,7 +17,7 @@ import torch
 
 from . import _lib
 from ._lib import (AA_ACT_GELU, AA_ACT_NONE, AA_ACT_QUICK_GELU, AA_ACT_SILU, AA_BF16, AA_F16, AA_F32, AaAttention, AaAttnOperand,
-                   AaBlend, AaConvGemm, AaFFFused, AaLinearRows, AaLinearFp8, AaQuantRowsFp8, AaDdimStepTok, AaDpmStep, AaDpmStepTok, AaEulerStepTok, AaGroupNorm, AaPackFrames, AaPackLatents, AaSeqSelfAttn, AaUnipcStepTok, AaFreeU, AaCfgRescale, AaWindow, AaWindowGather, AaWindowMerge, AaFreeInit)
+                   AaBlend, AaConvGemm, AaFFFused, AaLinearRows, AaLinearFp8, AaQuantRowsFp8, AaDdimStepTok, AaDpmStep, AaDpmStepTok, AaEulerStepTok, AaGroupNorm, AaPackFrames, AaPackLatents, AaSeqSelfAttn, AaUnipcStepTok, AaFreeU, AaCfgRescale, AaWindow, AaWindowGather, AaWindowMerge, AaFreeInit, AaKeepBlend)
 
 _DT = {torch.float16: AA_F16, torch.bfloat16: AA_BF16, torch.float32: AA_F32}
 
@@ -1713,4 +1713,46 @@ def freeinit_mix(x: torch.Tensor, n0: torch.Tensor, z: torch.Tensor, a: float, s
     elif workspace.dtype != torch.float32 or workspace.device != x.device:
         raise RuntimeError("freeinit_mix: the workspace must be fp32 on x's device")
     _run(lib.aa_freeinit_mix, C.byref(d), _ptr(workspace), workspace.numel() * 4, _stream(x))
+    return out
+
+
+# ------------------------------------------------------------------------------------- known-region blend
+def keep_blend(x: torch.Tensor, known: torch.Tensor, mask: torch.Tensor, a: float, s: float, noise: Optional[torch.Tensor] = None,
+               out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The known-region blend of inpainting samplers on fp32 planes x [clips, C, T, h, w] (or [clips, C, T, hw]), one launch
+    (aa_keep_blend): with kn = a * known + s * noise (noise None: s must be 0), out = x where mask >= 1, kn where mask <= 0 and
+    mask * x + (1 - mask) * kn between - the endpoints by selection: a mask of 1 hands x through bit for bit, a mask of 0 yields kn
+    whatever x holds.  `known`: fp32 / fp16 / bf16 [1 | clips, C, 1 | T, ...]; `mask`: fp32 / fp16 / bf16 [1 | clips, 1 | T, ...], or
+    the same with a channel axis of one, [1 | clips, 1, 1 | T, ...] (the motion mask's layout); `noise`: fp32 of x's shape.  A count of
+    one is broadcast.  `out`: None - in place, over x - or an fp32 tensor of x's shape that overlaps no operand.  Returns `out`, or x."""
+    lib = _lib.get()
+    if out is None:
+        out = x
+    _check(x, known, mask, noise, out)
+    if x.dim() not in (4, 5) or x.dtype != torch.float32 or x.numel() == 0:
+        raise RuntimeError("keep_blend: x must be fp32 [clips, C, T, h, w] or [clips, C, T, hw]")
+    clips, c, frames = x.shape[:3]
+    space = tuple(x.shape[3:])
+    for name, t in (("noise", noise), ("out", out)):
+        if t is not None and (t.dtype != torch.float32 or t.shape != x.shape or t.device != x.device):
+            raise RuntimeError(f"keep_blend: {name} must be fp32 of x's shape {tuple(x.shape)} on x's device")
+    for name, t in (("known", known), ("mask", mask)):
+        if t.dtype not in _DT or t.device != x.device:
+            raise RuntimeError(f"keep_blend: {name} must be fp32, fp16 or bf16 on x's device")
+    if known.dim() != x.dim() or known.shape[0] not in (1, clips) or known.shape[1] != c or known.shape[2] not in (1, frames) or tuple(known.shape[3:]) != space:
+        raise RuntimeError(f"keep_blend: known {tuple(known.shape)} is not [1 | {clips}, {c}, 1 | {frames}, {', '.join(map(str, space))}]")
+    m = mask
+    if m.dim() == x.dim() and m.shape[1] == 1:
+        m = m[:, 0]                                               # (a size-one axis: the memory is the same)
+    if m.dim() != x.dim() - 1 or m.shape[0] not in (1, clips) or m.shape[1] not in (1, frames) or tuple(m.shape[2:]) != space:
+        raise RuntimeError(f"keep_blend: mask {tuple(mask.shape)} is not [1 | {clips}, (1,) 1 | {frames}, {', '.join(map(str, space))}]")
+    if noise is None and float(s) != 0.0:
+        raise RuntimeError("keep_blend: s != 0 needs the noise operand")
+    d = AaKeepBlend()
+    d.x, d.out, d.known, d.mask, d.noise = _ptr(x), _ptr(out), _ptr(known), _ptr(mask), _ptr(noise)
+    d.clips, d.channels, d.frames, d.hw = clips, c, frames, x[0, 0, 0].numel()
+    d.known_clips, d.known_frames, d.mask_clips, d.mask_frames = known.shape[0], known.shape[2], m.shape[0], m.shape[1]
+    d.known_dtype, d.mask_dtype = _DT[known.dtype], _DT[mask.dtype]
+    d.a, d.s = float(a), float(s)
+    _run(lib.aa_keep_blend, C.byref(d), _stream(x))
     return out

@@ -151,6 +151,91 @@ def _context_schedule(context, num_frames):
     return context_windows(num_frames, c["frames"], c["overlap"], c["closed_loop"], c["weights"])
 
 
+KEEP_KEYS = ("latents", "mask", "noise", "image", "image_mask")
+
+
+def check_keep(keep, condition_latent=None, mask=None):
+    """The `keep` argument (the known-region blend of inpainting samplers: what the mask holds still stays on the input image while
+    sampling): None or False (off), True, or a mapping with keys from KEEP_KEYS -
+      `latents`     the known latents [1 | b, C, 1 | T, h, w]; default `condition_latent`
+      `mask`        [1 | b, 1, 1 | T, h, w] in the motion mask's convention, 1 = free, 0 = held; default the call's `mask`
+      `noise`       fp32 in the latents' shape; default None: one torch.randn per call, drawn by the pipeline
+      `image`       pixel-space known frames in [-1, 1], [b, 3, H, W] or [b, 3, 1 | f, H, W], pasted back after decoding; default None
+      `image_mask`  [H, W] or [1 | b, 1, 1 | f, H, W], required with `image` (and only then)
+    An unknown key, known latents or a mask that neither the mapping nor the call supplies, and `image` without `image_mask` (or the
+    reverse) raise ValueError.  Returns the completed dict (every key present), or None."""
+    if keep is None or keep is False:
+        return None
+    if keep is True:
+        keep = {}
+    if not hasattr(keep, "keys"):
+        raise ValueError(f"keep {keep!r}: None, true / false, or a mapping with keys from {sorted(KEEP_KEYS)}")
+    unknown = sorted(set(keep.keys()) - set(KEEP_KEYS))
+    if unknown:
+        raise ValueError(f"keep: unknown key(s) {unknown} (known: {sorted(KEEP_KEYS)})")
+    k = {key: keep[key] if key in keep.keys() else None for key in KEEP_KEYS}
+    if k["latents"] is None:
+        k["latents"] = condition_latent
+    if k["mask"] is None:
+        k["mask"] = mask
+    if k["latents"] is None:
+        raise ValueError("keep: no known latents - neither keep.latents nor `condition_latent` is given")
+    if k["mask"] is None:
+        raise ValueError("keep: no mask - neither keep.mask nor the call's `mask` is given")
+    if (k["image"] is None) != (k["image_mask"] is None):
+        raise ValueError("keep.image and keep.image_mask go together: the known frames and where they are pasted back")
+    return k
+
+
+def _keep_operands(k, x):
+    """The tensors of a completed `keep` dict as ops.keep_blend takes them for the fp32 latents `x` [b, C, T, h, w]: (known, mask,
+    noise) on x's device, contiguous, shapes checked (ValueError)."""
+    b, c, frames, h, w = x.shape
+    known = torch.as_tensor(k["latents"]).to(x.device)
+    m = torch.as_tensor(k["mask"]).to(x.device)
+    if not known.is_floating_point() or known.dtype not in ops._DT:
+        known = known.to(torch.float32)
+    if not m.is_floating_point() or m.dtype not in ops._DT:
+        m = m.to(torch.float32)
+    if known.dim() != 5 or known.shape[0] not in (1, b) or known.shape[1] != c or known.shape[2] not in (1, frames) or tuple(known.shape[3:]) != (h, w):
+        raise ValueError(f"keep.latents {tuple(known.shape)}: [1 | {b}, {c}, 1 | {frames}, {h}, {w}]")
+    if m.dim() != 5 or m.shape[0] not in (1, b) or m.shape[1] != 1 or m.shape[2] not in (1, frames) or tuple(m.shape[3:]) != (h, w):
+        raise ValueError(f"keep.mask {tuple(m.shape)}: [1 | {b}, 1, 1 | {frames}, {h}, {w}]")
+    noise = k["noise"]
+    if noise is not None:
+        noise = torch.as_tensor(noise)
+        if noise.dtype != torch.float32 or tuple(noise.shape) != tuple(x.shape):
+            raise ValueError(f"keep.noise: fp32 in the latents' shape {tuple(x.shape)}")
+        noise = noise.to(x.device).contiguous()
+    return known.contiguous(), m.contiguous(), noise
+
+
+def _keep_image_operands(k, video):
+    """(image, image_mask) of a completed `keep` dict for the decoded fp32 video [b, 3, f, H, W]: fp32 on its device, the image as
+    [b, 3, 1 | f, H, W], the mask as [1 | b, 1, 1 | f, H, W]."""
+    b, c, f, H, W = video.shape
+    img = torch.as_tensor(k["image"]).to(device=video.device, dtype=torch.float32)
+    if img.dim() == 4:
+        img = img[:, :, None]
+    m = torch.as_tensor(k["image_mask"]).to(device=video.device, dtype=torch.float32)
+    if m.dim() == 2:
+        m = m[None, None, None]
+    if img.dim() != 5 or img.shape[0] not in (1, b) or img.shape[1] != c or img.shape[2] not in (1, f) or tuple(img.shape[3:]) != (H, W):
+        raise ValueError(f"keep.image {tuple(img.shape)}: [{b}, {c}, {H}, {W}] or [{b}, {c}, 1 | {f}, {H}, {W}]")
+    if m.dim() != 5 or m.shape[0] not in (1, b) or m.shape[1] != 1 or m.shape[2] not in (1, f) or tuple(m.shape[3:]) != (H, W):
+        raise ValueError(f"keep.image_mask {tuple(m.shape)}: [{H}, {W}] or [1 | {b}, 1, 1 | {f}, {H}, {W}]")
+    return img.contiguous(), m.contiguous()
+
+
+def _keep_scalars(sched, ts, i):
+    """(a, s) of the blend behind step i of the schedule `ts`: (sqrt(abar), sqrt(1 - abar)) at ts[i + 1], the level the solver has just
+    reached, in float64 from `scheduler.alphas_cumprod`; (1, 0) behind the last step (the known latents themselves, no noise read)."""
+    if i + 1 >= len(ts):
+        return 1.0, 0.0
+    abar = float(sched.alphas_cumprod[int(ts[i + 1])])
+    return abar ** 0.5, (1.0 - abar) ** 0.5
+
+
 def tensor2vid(video):
     """diffusers 0.24 tensor2vid (mean = std = 0.5): [b,c,f,h,w] -> list of f uint8 [h, b*w, c] frames."""
     video = (video.float() * 0.5 + 0.5).clamp(0, 1)
@@ -279,7 +364,7 @@ class LatentToVideoPipeline(PretrainedPipeline):
 
     # ------------------------------------------------------------------ denoising
     def denoise(self, latents, prompt_embeds, condition_latent, mask, motion, timesteps, guidance_scale,
-                callback=None, callback_steps=1, eta=0.0, generator=None, guidance_rescale=0.0, context=None):
+                callback=None, callback_steps=1, eta=0.0, generator=None, guidance_rescale=0.0, context=None, keep=None):
         """The hot loop (reference pipeline.py:163-198).  `prompt_embeds` already holds [uncond; text]
         when guidance is on.  Latents are kept in fp32.
 
@@ -298,7 +383,15 @@ class LatentToVideoPipeline(PretrainedPipeline):
         ops.window_gather_latents into the session's `sample`, the session, (ops.cfg_rescale_tokens, per window,) and
         ops.window_merge_tokens, which blends the window's prediction into one token matrix of the clip's length (both guidance halves:
         a frame held by one window keeps the UNet's bits); then the same solver kernel runs once on that matrix with the same guidance.  The solver state is sized from the long latents.  None, or a window
-        that holds the whole clip: the loop of before, no window op."""
+        that holds the whole clip: the loop of before, no window op.
+        `keep` (check_keep; the known-region blend of inpainting samplers): behind the solver kernel of step i one ops.keep_blend, in
+        place on the whole clip's fp32 latents (under context windows: the long buffer), overwrites what the mask holds still with
+        a_i * known + s_i * noise, (a_i, s_i) = (sqrt(abar), sqrt(1 - abar)) at the NEXT timestep - the level the solver has just
+        reached - and (1, 0) behind the last step, so the held region ends as the known latents bit for bit; where the mask is 1 the
+        launch hands the latents through untouched.  One noise tensor serves the whole call (and every FreeInit iteration).  The
+        callback sees the blended latents; nothing is blended before the first step.  Under a guidance pair both ranks blend alike
+        (their generators must agree, as for eta > 0).  UniPC is refused (`_keep_setup`).  None / False: no launch, no randn."""
+        k = self._keep_setup(keep, condition_latent, mask, latents, generator)
         cfg = guidance_scale > 1.0
         rescale = _check_guidance_rescale(guidance_rescale) if cfg else 0.0
         windows = _context_schedule(context, latents.shape[2])
@@ -306,7 +399,7 @@ class LatentToVideoPipeline(PretrainedPipeline):
         unet = self.unet
         if not (isinstance(sched, (DPMSolverMultistepScheduler, DDIMScheduler, UniPCMultistepScheduler)) and hasattr(unet, "session")):
             return self._denoise_generic(latents, prompt_embeds, condition_latent, mask, motion, timesteps, guidance_scale,
-                                         callback, callback_steps, eta, generator, guidance_rescale=guidance_rescale, context=context)
+                                         callback, callback_steps, eta, generator, guidance_rescale=guidance_rescale, context=context, keep=k)
         dev = latents.device
         b0, _, frames, h, w = latents.shape
         wf = frames if windows is None else len(windows[0][0])  # frames the UNet sees at a time
@@ -349,6 +442,8 @@ class LatentToVideoPipeline(PretrainedPipeline):
             halves = 2 if cfg and rescale == 0.0 else 1         # a UNet output of the clip's length: [uncond clips | text clips]
             merged = torch.zeros((halves * b0 * (frames + 1) * h * w, 8), dtype=unet.dtype, device=dev)
         step = self._solver_step(x, eta, generator)
+        if k is not None:
+            known, held, knoise = _keep_operands(k, x)
         for i, t in enumerate(ts):
             if windows is None:
                 tok = tokens()
@@ -363,6 +458,9 @@ class LatentToVideoPipeline(PretrainedPipeline):
                     ops.window_merge_tokens(wtok, acc, merged, win, None if rescale > 0.0 else guidance)
                 tok = merged
             step(tok, None if rescale > 0.0 else guidance, t, i, sess.inputs["t"], float(ts[i + 1]) if i + 1 < len(ts) else float(t))
+            if k is not None:
+                a, s = _keep_scalars(sched, ts, i)
+                ops.keep_blend(x, known, held, a, s, noise=knoise if i + 1 < len(ts) else None)
             if callback is not None and i % callback_steps == 0:
                 callback(i, t, x)
         return x.clone()
@@ -395,6 +493,25 @@ class LatentToVideoPipeline(PretrainedPipeline):
                 ops.cfg_dpm_step_tokens(tokens, x, x0_prev, None, guidance, k, next_t=next_t, next_t_value=next_t_value)
         return step
 
+    def _keep_setup(self, keep, condition_latent, mask, latents, generator):
+        """check_keep for this pipeline and these latents: the completed dict with its `noise` in place - left out, it is drawn here,
+        one torch.randn of the latents' shape (fp32, the caller's generator, a generator on another device handled as
+        `_free_init_noise` handles it) - or None (off: nothing is drawn).  A completed dict passes through unchanged, so `__call__`
+        draws once and every `denoise` of the call blends with the same noise.  Raises ValueError, before any device work, for a
+        scheduler the blend cannot serve."""
+        k = check_keep(keep, condition_latent, mask)
+        if k is None:
+            return None
+        if isinstance(self.scheduler, UniPCMultistepScheduler):
+            raise ValueError("keep: not available with UniPCMultistepScheduler - its corrector rebuilds the sample from its own `last_sample` "
+                             "and never reads the sample it is handed, so the blend would be dropped from the trajectory while still "
+                             "steering the UNet; sample with DPM-Solver++ or DDIM")
+        if not hasattr(self.scheduler, "alphas_cumprod"):
+            raise ValueError(f"keep: {type(self.scheduler).__name__} has no `alphas_cumprod` to take the noise level of a step from")
+        if k["noise"] is None:
+            k["noise"] = _free_init_noise(latents, generator)
+        return k
+
     @staticmethod
     def _unipc_state(x):
         """The four fp32 buffers a UniPC run keeps next to the latents: [corrected sample, m of the previous step, of the second
@@ -402,15 +519,17 @@ class LatentToVideoPipeline(PretrainedPipeline):
         return [torch.zeros_like(x) for _ in range(4)]
 
     def _denoise_generic(self, latents, prompt_embeds, condition_latent, mask, motion, timesteps, guidance_scale,
-                         callback=None, callback_steps=1, eta=0.0, generator=None, guidance_rescale=0.0, context=None):
+                         callback=None, callback_steps=1, eta=0.0, generator=None, guidance_rescale=0.0, context=None, keep=None):
         """Any scheduler with a diffusers-style `step()`: the UNet through its module `forward`, guidance and the update as
         torch expressions (the reference's own sequence, pipeline.py:165-192).  `eta` / `generator` go to a `step()` that
         names them (diffusers' prepare_extra_step_kwargs, pipeline.py:156); DDIM's variance noise is drawn here exactly as
         the fused loop draws it, so both consume the generator alike.  `guidance_rescale` > 0 under guidance applies
         `rescale_noise_cfg` to the guided prediction.  `context` with a window shorter than the clip (check_context): per step the
         module forward, guidance and `rescale_noise_cfg` run per window of schedulers.context_windows, the guided predictions are
-        summed in fp32 with the windows' per-frame weights, and `step()` is applied once to the whole clip."""
+        summed in fp32 with the windows' per-frame weights, and `step()` is applied once to the whole clip.  `keep` (check_keep): the
+        blend of `denoise` behind every `step()`, as torch expressions with the same selection at the mask's endpoints."""
         import inspect
+        k = self._keep_setup(keep, condition_latent, mask, latents, generator)
         cfg = guidance_scale > 1.0
         rescale = _check_guidance_rescale(guidance_rescale) if cfg else 0.0
         windows = _context_schedule(context, latents.shape[2])
@@ -424,6 +543,9 @@ class LatentToVideoPipeline(PretrainedPipeline):
             extra["generator"] = generator
         x = latents.float().contiguous()
         cond = torch.cat([condition_latent, condition_latent]) if cfg else condition_latent     # :160-161
+        if k is not None:
+            known, held, knoise = _keep_operands(k, x)
+            known, held, ts = known.float(), held.float(), [int(t) for t in timesteps]
 
         def predict(xs, t):
             """The (guided, rescaled) fp32 prediction for the latents `xs` - the clip, or one window of it."""
@@ -452,6 +574,10 @@ class LatentToVideoPipeline(PretrainedPipeline):
             flat = sched.step(e.permute(0, 2, 1, 3, 4).reshape(b * f, c, h, w), t,
                               x.permute(0, 2, 1, 3, 4).reshape(b * f, c, h, w), **extra).prev_sample
             x = flat.reshape(b, f, c, h, w).permute(0, 2, 1, 3, 4).contiguous()
+            if k is not None:
+                a, s = _keep_scalars(sched, ts, i)
+                kn = a * known + s * knoise if i + 1 < len(ts) else a * known
+                x = torch.where(held >= 1, x, torch.where(held <= 0, kn, held * x + (1 - held) * kn)).contiguous()
             if callback is not None and i % callback_steps == 0:
                 callback(i, t, x)
         return x
@@ -461,8 +587,12 @@ class LatentToVideoPipeline(PretrainedPipeline):
                  guidance_scale=9.0, negative_prompt=None, eta=0.0, generator=None, latents=None,
                  prompt_embeds=None, negative_prompt_embeds=None, output_type="np", return_dict=True,
                  callback=None, callback_steps=1, cross_attention_kwargs=None, condition_latent=None,
-                 mask=None, timesteps=None, motion=None, guidance_rescale=0.0, context=None, free_init=None):
-        """`free_init` (a mapping, check_free_init; None: what `enable_free_init` set, off by default) with num_iters > 1 - FreeInit:
+                 mask=None, timesteps=None, motion=None, guidance_rescale=0.0, context=None, free_init=None, keep=None):
+        """`keep` (check_keep; None / False: off, the default): the known-region blend of inpainting samplers - what the mask holds still
+        (mask 0) is put back on the known latents, noised to the step's level, behind every solver step (`denoise`), and with
+        keep.image / keep.image_mask the known pixels are pasted over the decoded fp32 video by one more ops.keep_blend in front of
+        `tensor2vid`.  The noise of the call is drawn once, here, in front of the first FreeInit iteration.  Off: no launch, no randn.
+        `free_init` (a mapping, check_free_init; None: what `enable_free_init` set, off by default) with num_iters > 1 - FreeInit:
         the clip is sampled num_iters times.  Iteration 0 starts from the caller's latents n0; iteration i >= 1 from
         ops.freeinit_mix(x, n0, z): the previous result x re-noised with n0 to the last training timestep, low-passed over the clip's
         whole (frames, h, w), the high frequencies taken from z = one torch.randn of the latents' shape (fp32, the caller's generator).
@@ -472,6 +602,7 @@ class LatentToVideoPipeline(PretrainedPipeline):
         iterations (diffusers rounds them to the model dtype).  num_iters = 1, or off: one `denoise`, no extra launch, no extra randn."""
         if latents is None:
             raise ValueError("LatentToVideoPipeline expects caller-prepared `latents` (reference pipeline.py:153)")
+        keep = self._keep_setup(keep, condition_latent, mask, latents, generator)
         fi = check_free_init(free_init) if free_init is not None else self.free_init
         iters = fi["num_iters"] if fi is not None else 1
         fast = iters > 1 and fi["use_fast_sampling"]
@@ -495,12 +626,15 @@ class LatentToVideoPipeline(PretrainedPipeline):
             ts = self.scheduler.timesteps if timesteps is None else timesteps
             x = self.denoise(x, prompt_embeds, condition_latent, mask, motion, [int(t) for t in ts],
                              guidance_scale, callback, callback_steps, eta=eta, generator=generator, guidance_rescale=guidance_rescale,
-                             context=context)
+                             context=context, keep=keep)
         latents = x.to(self.unet.dtype)
         if self.vae is None or output_type == "latent":
             video = None
         else:
             video_tensor = self.decode_latents(latents)
+            if keep is not None and keep["image"] is not None:  # (decode_latents returns a permuted view: the kernel wants the planes dense)
+                image, image_mask = _keep_image_operands(keep, video_tensor)
+                video_tensor = ops.keep_blend(video_tensor.contiguous(), image, image_mask, 1.0, 0.0)
             video = video_tensor if output_type == "pt" else tensor2vid(video_tensor)
         if not return_dict:
             return (video, latents)

@@ -814,6 +814,40 @@ typedef struct AaFreeInit {
 size_t aa_freeinit_workspace(const AaFreeInit* d);
 int aa_freeinit_mix(const AaFreeInit* d, void* workspace, size_t workspace_bytes, void* stream);
 
+/* aa_keep_blend (added under version 110: no existing descriptor or entry point changed, so AA_VERSION stays): the known-region blend of
+ * inpainting samplers (Avrahami et al., "Blended Latent Diffusion"; diffusers' inpaint pipelines; not in the reference) - behind a solver
+ * step the region the motion mask holds still is overwritten with the known latents noised to the level the sampler has just reached,
+ * and behind the VAE the known pixels are pasted back.  One launch on contiguous fp32 planes x [clips][channels][frames][hw]
+ * (the latents [b, 4, T, h, w]; the decoded video [b, 3, f, H, W]):
+ *   kn  = a * known + s * noise                        (noise NULL: s must be 0 and kn = a * known)
+ *   out = x                   where m >= 1
+ *         kn                  where m <= 0
+ *         m * x + (1 - m) kn  otherwise                (fp32)
+ * The endpoints are selected, not computed: m == 1 hands x through bit for bit whatever known and noise hold (NaN, Inf), m == 0 yields
+ * kn whatever x holds.  `known` is [known_clips][channels][known_frames][hw] and `mask` [mask_clips][mask_frames][hw] (no channel
+ * axis), each fp32, fp16 or bf16; a count of 1 is broadcast over the clips / frames (the condition image is one frame).  `out` is x
+ * itself (in place) or a buffer disjoint from every operand.  hw % 4 == 0 with every pointer 16-byte aligned selects the form with
+ * 16-byte accesses; anything else runs element by element.  No atomics: a replay or a second call repeats the bits.
+ * Refused with nothing launched - AA_E_SHAPE: a null descriptor, x, out, known or mask; clips, channels, frames or hw < 1; more than
+ * 65535 frames or clips * channels; 2^31 or more elements; a broadcast count other than 1 or the full one; a or s not finite; a null
+ * noise with s != 0; an `out` that overlaps x other than as the identical pointer, or known, mask or noise at all.  AA_E_DTYPE: a
+ * known_dtype / mask_dtype other than AA_F32 / AA_F16 / AA_BF16.  AA_E_ALIGN: x / out / noise not 4-byte aligned, known / mask not
+ * aligned to their element size. */
+typedef struct AaKeepBlend {
+    const float* x;           /* fp32 [clips][channels][frames][hw] */
+    float* out;               /* fp32, x's layout; may be x */
+    const void* known;        /* known_dtype [known_clips][channels][known_frames][hw] */
+    const void* mask;         /* mask_dtype [mask_clips][mask_frames][hw]: 1 = keep x, 0 = take the known value */
+    const float* noise;       /* fp32, x's layout, or NULL */
+    int32_t clips, channels, frames, hw;
+    int32_t known_clips, known_frames;   /* 1 or clips / 1 or frames */
+    int32_t mask_clips, mask_frames;
+    int32_t known_dtype, mask_dtype;     /* AA_F32 / AA_F16 / AA_BF16 */
+    float a, s;
+} AaKeepBlend;
+
+int aa_keep_blend(const AaKeepBlend* d, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
