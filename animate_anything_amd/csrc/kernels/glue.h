@@ -16,6 +16,17 @@
 
 namespace aa {
 
+// 2^(c x) with c = c_hi + c_lo.  The product c_hi * x is rounded to fp32 before the exponential sees it: a relative error of
+// |c x| 2^-24 ln 2 in the result, 1e-6 where c x = -30 - more than a 16-bit store of the far tail of a sigmoid forgives when the
+// value sits at a rounding tie.  The rounded-off part (one fma) and c_lo x go back in to first order; exponents past 126 are held
+// there (2^126 in a denominator is the same zero, and no inf * 0 arises).
+__device__ __forceinline__ float exp2_scaled(float c_hi, float c_lo, float x) {
+    const float a = c_hi * x;
+    const float r = __builtin_fmaf(c_hi, x, -a) + c_lo * x;
+    const float e = fast_exp2(fminf(a, 126.0f));
+    return __builtin_fmaf(e, 0.6931471805599453f * r, e);
+}
+
 template <typename T>
 __global__ void __launch_bounds__(256) timestep_embed_kernel(const float* t, T* out, int n, int dim) {
     const int half = dim >> 1;
@@ -191,7 +202,7 @@ __global__ void __launch_bounds__(256) blend_kernel(const AaBlend p) {
             for (int e = 0; e < 8; ++e) v[e] = gelu_erf_f(v[e]);
         } else if (p.act == AA_ACT_QUICK_GELU) {
 #pragma unroll
-            for (int e = 0; e < 8; ++e) v[e] = v[e] / (1.0f + __expf(-1.702f * v[e]));
+            for (int e = 0; e < 8; ++e) v[e] = v[e] / (1.0f + exp2_scaled(-2.4554669857025146f, 2.6109498563187117e-08f, v[e]));      // exp(-1.702 v): -1.702 log2(e) = hi + lo
         }
 #pragma unroll
         for (int e = 0; e < 8; ++e) o.e[e] = (T)v[e];

@@ -18,6 +18,7 @@
 #pragma once
 #include "dev.h"
 #include "aa_mi355.h"
+#include "row_mean.h"
 
 namespace aa {
 
@@ -154,7 +155,7 @@ __global__ void __launch_bounds__(64 * NW, NW / 2) linear_rows_kernel(const AaLi
         for (int ks = 0; ks < NKS; ++ks)
 #pragma unroll
             for (int k = 0; k < 4; ++k) sum = dot2_f32(T(), xf[ks][k], ones_pair(T()), sum);
-        const float mean = wave_sum_halves(sum) * (1.0f / (float)C);
+        const float mean = row_mean(wave_sum_halves(sum), C);
         const f32x2 nmean2 = f32x2{-mean, -mean};
         f32x2 var2 = f32x2{0.0f, 0.0f};
 #pragma unroll
@@ -167,13 +168,13 @@ __global__ void __launch_bounds__(64 * NW, NW / 2) linear_rows_kernel(const AaLi
             }
         }
         const float rstd = 1.0f / sqrtf(wave_sum_halves(var2[0] + var2[1]) * (1.0f / (float)C) + p.ln_eps);
-        const f32x2 rstd2 = f32x2{rstd, rstd}, off2 = f32x2{-mean * rstd, -mean * rstd};
+        const f32x2 rstd2 = f32x2{rstd, rstd};      // (x - mean) first: a constant row normalises to exactly 0, whatever rstd is
 #pragma unroll
         for (int ks = 0; ks < NKS; ++ks) {
             Pack8<T> v; v.raw = xf[ks];
 #pragma unroll
             for (int e = 0; e < 8; e += 2) {
-                const f32x2 y = __builtin_elementwise_fma(f32x2{(float)v.e[e], (float)v.e[e + 1]}, rstd2, off2);
+                const f32x2 y = (f32x2{(float)v.e[e], (float)v.e[e + 1]} + nmean2) * rstd2;
                 v.e[e] = (T)y[0]; v.e[e + 1] = (T)y[1];
             }
             xf[ks] = v.raw;

@@ -656,6 +656,8 @@ def _conv_gemm_desc(x0, pw, g, x1=None, rowvec=None, rowvec_div=1, residual=None
     d.tile, d.k_splits = -1, K_SPLITS
     key = (d.dtype, g.n_img, g.h_in, g.w_in, d.h_virt, d.w_virt, g.h_out, g.w_out, g.stride, pw.kh, pw.kw, c0, c1,
            pw.n_out, d.geglu, residual is not None) + (("ln",) if ln_stats is not None else ()) + (("stats",) if row_stats else ())
+    if odt != x0.dtype:                                   # another output type runs the gather kernel: never the tile tuned for the 16-bit call of the same shape
+        key += (("out", d.out_dtype),)
     return d, key, out, b
 
 
