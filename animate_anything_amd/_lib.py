@@ -192,6 +192,14 @@ class AaCfgRescale(C.Structure):
     ]
 
 
+class AaApg(C.Structure):
+    _fields_ = [
+        ("tokens", C.c_void_p), ("out", C.c_void_p), ("momentum_buf", C.c_void_p), ("stats", C.c_void_p),
+        ("clips", C.c_int32), ("channels", C.c_int32), ("frames", C.c_int32), ("hw", C.c_int32), ("ld", C.c_int32), ("out_ld", C.c_int32),
+        ("guidance", C.c_float), ("eta", C.c_float), ("norm_threshold", C.c_float), ("momentum", C.c_float), ("dtype", C.c_int32),
+    ]
+
+
 AA_WINDOW_MAX = 64
 
 
@@ -292,6 +300,8 @@ PROTOTYPES = {
     "aa_freeu_tokens": _launch(AaFreeU),
     "aa_cfg_rescale_workspace": (_Z, [_P(AaCfgRescale)]),
     "aa_cfg_rescale_tokens": (_I, [_P(AaCfgRescale), _V, _Z, _V]),
+    "aa_apg_workspace": (_Z, [_P(AaApg)]),
+    "aa_apg_tokens": (_I, [_P(AaApg), _V, _Z, _V]),
     "aa_window_gather_latents": _launch(AaWindowGather),
     "aa_window_merge_tokens": _launch(AaWindowMerge),
     "aa_freeinit_workspace": (_Z, [_P(AaFreeInit)]),

@@ -64,7 +64,7 @@ def build(force=False, verbose=False, probe=False, ablate=0, variant=None):
     # attention / norm / glue kernels' headers through aa_api_impl.h but instantiate nothing of them (AA_TU_TILES_ONLY), so edits
     # there rebuild the C-ABI unit alone (~1.5 of the ~4 minutes).  Key = sha256 of (flags, the unit's sources).
     import hashlib
-    api_only = {"attention.h", "seq_attention.h", "norm.h", "glue.h", "freeu.h", "cfg_rescale.h", "window.h", "freeinit.h", "keep.h", "ff_fused.h", "linear_rows.h", "linear_fp8.h"}
+    api_only = {"attention.h", "seq_attention.h", "norm.h", "glue.h", "freeu.h", "cfg_rescale.h", "apg.h", "window.h", "freeinit.h", "keep.h", "ff_fused.h", "linear_rows.h", "linear_fp8.h"}
 
     def dep_hash(job):
         src, _ = job

@@ -22,6 +22,7 @@
 #include "kernels/glue.h"
 #include "kernels/freeu.h"
 #include "kernels/cfg_rescale.h"
+#include "kernels/apg.h"
 #include "kernels/window.h"
 #include "kernels/freeinit.h"
 #include "kernels/keep.h"
@@ -1340,6 +1341,54 @@ int aa_cfg_rescale_tokens(const AaCfgRescale* d, void* workspace, size_t workspa
         AA_LAUNCH((cfg_rescale_apply_kernel<T>), grid, block, CR_LDS_BYTES, stream, *d, (const double*)ws);
     });
     return finish("cfg_rescale_tokens");
+}
+
+static bool apg_geometry_ok(const AaApg* d) {
+    if (d->clips < 1 || d->channels < 1 || d->frames < 1 || d->hw < 1 || d->clips > 65535) return false;
+    return (int64_t)2 * d->clips * ((int64_t)d->frames + 1) * d->hw < ((int64_t)1 << 31);
+}
+
+size_t aa_apg_workspace(const AaApg* d) {
+    if (!d || !apg_geometry_ok(d)) return 0;
+    return (size_t)d->clips * aa::apg_parts(*d) * 3 * sizeof(double);
+}
+
+int aa_apg_tokens(const AaApg* d, void* workspace, size_t workspace_bytes, void* stream) {
+    using namespace aa;
+    if (!d || !d->tokens || !d->out) return fail(AA_E_SHAPE, "apg_tokens: null operand");
+    if (!apg_geometry_ok(d))
+        return fail(AA_E_SHAPE, "apg_tokens: bad geometry (clips %d, channels %d, frames %d, hw %d)", d->clips, d->channels, d->frames, d->hw);
+    if (d->ld < d->channels || d->out_ld < d->channels) return fail(AA_E_SHAPE, "apg_tokens: a row pitch is smaller than the channel count");
+    if (!finite_f32(&d->guidance) || !finite_f32(&d->eta) || !finite_f32(&d->norm_threshold) || !finite_f32(&d->momentum))
+        return fail(AA_E_SHAPE, "apg_tokens: guidance, eta, norm_threshold and momentum must be finite");
+    if (d->norm_threshold < 0.0f) return fail(AA_E_SHAPE, "apg_tokens: norm_threshold must not be negative (0: off)");
+    if (d->momentum <= -1.0f || d->momentum >= 1.0f) return fail(AA_E_SHAPE, "apg_tokens: momentum must lie in (-1, 1)");
+    if ((d->momentum != 0.0f) != (d->momentum_buf != nullptr))
+        return fail(AA_E_SHAPE, "apg_tokens: momentum_buf goes with momentum != 0, and only with it");
+    if (d->dtype != AA_F16 && d->dtype != AA_BF16) return fail(AA_E_DTYPE, "apg_tokens: unsupported dtype %d", d->dtype);
+    const size_t need = aa_apg_workspace(d);
+    if (!workspace || workspace_bytes < need) return fail(AA_E_WORKSPACE, "apg_tokens: workspace %zu < %zu bytes", workspace_bytes, need);
+    if (!aligned_to(d->tokens, 2) || !aligned_to(d->out, 2) || !aligned_to(d->momentum_buf, 4) || !aligned_to(d->stats, 4) || !aligned_to(workspace, 8))
+        return fail(AA_E_ALIGN, "apg_tokens: tokens / out must be 2-byte, momentum_buf / stats 4-byte, the workspace 8-byte aligned");
+    const int64_t rows = (int64_t)d->clips * (d->frames + 1) * d->hw;
+    const Span sp[5] = {{d->tokens, ((2 * rows - 1) * d->ld + d->channels) * 2}, {d->out, ((rows - 1) * d->out_ld + d->channels) * 2},
+                        {d->momentum_buf, (int64_t)d->clips * d->frames * d->hw * d->channels * 4}, {d->stats, (int64_t)d->clips * 8},
+                        {workspace, (int64_t)need}};
+    for (int i = 0; i < 5; ++i)
+        for (int j = i + 1; j < 5; ++j) {
+            if (!spans_overlap(sp[i], sp[j])) continue;
+            if (i == 0 && j == 1 && d->tokens == d->out && d->ld == d->out_ld) continue;
+            return fail(AA_E_SHAPE, i == 0 && j == 1 ? "apg_tokens: out may be the unconditional half of tokens (same pointer and pitch) or a separate buffer, not overlap it"
+                                                     : "apg_tokens: momentum_buf, stats and the workspace must not overlap the matrices or each other");
+        }
+    const dim3 grid((unsigned)apg_parts(*d), (unsigned)d->clips), block(APG_THREADS);
+    double* ws = (double*)workspace;
+    with_dtype16(d->dtype, [&](auto t) {
+        using T = typename decltype(t)::type;
+        AA_LAUNCH((apg_moments_kernel<T>), grid, block, APG_LDS_BYTES, stream, *d, ws);
+        AA_LAUNCH((apg_apply_kernel<T>), grid, block, APG_LDS_BYTES, stream, *d, (const double*)ws);
+    });
+    return finish("apg_tokens");
 }
 
 // The window a context-window descriptor carries by value: slot count, frame indices in range and distinct (two slots on one frame

@@ -9,7 +9,9 @@ num_frames,width,height,num_inference_steps,guidance_scale,fps}`, `seed`, `motio
 of DPM-Solver++, `freeu: {s1: .., s2: .., b1: .., b2: ..}` for diffusers' FreeU switch and `validation_data.guidance_rescale`
 (a number in [0, 1], absent = 0) for diffusers' `guidance_rescale`, and `validation_data.context: {frames, overlap, weights,
 closed_loop}` for context windows - `num_frames` beyond the UNet's frame window - and `validation_data.free_init: {num_iters,
-use_fast_sampling, method, order, spatial_stop_frequency, temporal_stop_frequency}` for diffusers' FreeInit.
+use_fast_sampling, method, order, spatial_stop_frequency, temporal_stop_frequency}` for diffusers' FreeInit and
+`validation_data.apg: {eta, norm_threshold, momentum}` for Adaptive Projected Guidance (not together with `guidance_rescale`)
+(INTEGRATION.md section 1).
 The third-party pieces the reference pulls in and that do not exist in this image are replaced by small
 equivalents: OmegaConf -> PyYAML + dot-list merge, `VaeImageProcessor.preprocess` -> PIL lanczos resize + [-1,1]
 scaling, torchvision `ToTensor`/`Resize(antialias=False)` -> torch bilinear interpolate, imageio -> PIL GIF writer.
@@ -32,7 +34,7 @@ import yaml
 from PIL import Image
 
 from .pipeline import (DDPM_forward_timesteps, LatentToVideoPipeline, calculate_latent_motion_score,
-                       check_context, tensor_to_vae_latent)
+                       check_apg, check_context, tensor_to_vae_latent)
 from .schedulers import DDIMScheduler, DDPMScheduler, DPMSolverMultistepScheduler, UniPCMultistepScheduler, check_free_init
 from .unet3d import UNet3DConditionModel
 from .vae import AutoencoderKL
@@ -199,7 +201,7 @@ def eval(pipeline, validation_data, out_file, index, forward_t=25, preview=True,
             guidance_scale=validation_data.guidance_scale, condition_latent=input_image_latents, mask=mask,
             motion=[motion_strength], return_dict=False, timesteps=timesteps,
             guidance_rescale=_check_guidance_rescale(validation_data), context=_check_context(validation_data),
-            free_init=_check_free_init(validation_data), keep=keep, **prompt_kwargs)
+            free_init=_check_free_init(validation_data), keep=keep, apg=_check_apg(validation_data), **prompt_kwargs)
     if preview:
         save_gif(out_file, video_frames, validation_data.get("fps", 8))
     real_motion_strength = calculate_latent_motion_score(video_latents.float()).cpu().numpy()[0]
@@ -254,6 +256,16 @@ def _check_free_init(validation_data):
     return check_free_init(dict(free_init) if isinstance(free_init, dict) else free_init)
 
 
+def _check_apg(validation_data):
+    """`validation_data.apg`: absent (None: off) or `{eta, norm_threshold, momentum}` (pipeline.check_apg: any key may be left out, an
+    unknown one is refused); not together with a `guidance_rescale` above 0.  Returns the completed dict or None."""
+    apg = validation_data.get("apg") if validation_data is not None else None
+    apg = check_apg(dict(apg) if isinstance(apg, dict) else apg)
+    if apg is not None and _check_guidance_rescale(validation_data) > 0.0:
+        raise ValueError("validation_data.apg and validation_data.guidance_rescale > 0 cannot be combined")
+    return apg
+
+
 def _check_keep_unmasked(validation_data, sampler=None):
     """`validation_data.keep_unmasked`: absent (false) or a boolean - true: the region the motion mask holds still is kept on the input
     image while sampling (pipeline `keep`).  Not with `sampler: unipc`, whose corrector never reads the sample it is handed
@@ -279,6 +291,7 @@ def batch_eval(unet, text_encoder, vae, tokenizer, scheduler_config, validation_
     _check_guidance_rescale(validation_data)
     _check_context(validation_data)
     _check_free_init(validation_data)
+    _check_apg(validation_data)
     _check_keep_unmasked(validation_data, sampler)
     unet.eval()
     scheduler = SAMPLERS[sampler].from_config(scheduler_config)
@@ -319,6 +332,7 @@ def main_eval(pretrained_model_path, validation_data, seed=None, motion_mask=Non
     _check_guidance_rescale(validation_data)
     _check_context(validation_data)
     _check_free_init(validation_data)
+    _check_apg(validation_data)
     _check_keep_unmasked(validation_data, sampler)
     from . import distributed as D
     rank, world, _dev = D.init()

@@ -17,7 +17,7 @@ import torch
 
 from . import _lib
 from ._lib import (AA_ACT_GELU, AA_ACT_NONE, AA_ACT_QUICK_GELU, AA_ACT_SILU, AA_BF16, AA_F16, AA_F32, AaAttention, AaAttnOperand,
-                   AaBlend, AaConvGemm, AaFFFused, AaLinearRows, AaLinearFp8, AaQuantRowsFp8, AaDdimStepTok, AaDpmStep, AaDpmStepTok, AaEulerStepTok, AaGroupNorm, AaPackFrames, AaPackLatents, AaSeqSelfAttn, AaUnipcStepTok, AaFreeU, AaCfgRescale, AaWindow, AaWindowGather, AaWindowMerge, AaFreeInit, AaKeepBlend)
+                   AaBlend, AaConvGemm, AaFFFused, AaLinearRows, AaLinearFp8, AaQuantRowsFp8, AaDdimStepTok, AaDpmStep, AaDpmStepTok, AaEulerStepTok, AaGroupNorm, AaPackFrames, AaPackLatents, AaSeqSelfAttn, AaUnipcStepTok, AaFreeU, AaCfgRescale, AaApg, AaWindow, AaWindowGather, AaWindowMerge, AaFreeInit, AaKeepBlend)
 
 _DT = {torch.float16: AA_F16, torch.bfloat16: AA_BF16, torch.float32: AA_F32}
 
@@ -1575,6 +1575,48 @@ def cfg_rescale_tokens(tokens: torch.Tensor, clips: int, channels: int, frames: 
     if ws is None or ws.numel() * 8 < nbytes:
         ws = _CFG_RESCALE_WS[key] = torch.empty(max(nbytes // 8, 1), dtype=torch.float64, device=tokens.device)
     _run(lib.aa_cfg_rescale_tokens, C.byref(d), _ptr(ws), ws.numel() * 8, _stream(tokens))
+    return out
+
+
+# ------------------------------------------------------------------------------------- adaptive projected guidance
+_APG_WS = {}
+
+
+def apg_tokens(tokens: torch.Tensor, clips: int, channels: int, frames: int, hw: int, guidance: float, eta: float, norm_threshold: float,
+               momentum: float, momentum_buf: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
+               stats: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Adaptive Projected Guidance (Sadat et al. 2024, per clip) on the UNet's token-layout output `tokens`
+    [2*clips*(frames+1)*hw, >= channels] (unconditional clips first; rows may be pitched: stride(0) >= channels, stride(1) == 1): with
+    d = t - u (momentum != 0: d = r = d + momentum * r_prev, `momentum_buf` - fp32, clips*frames*hw*channels elements, dense - holding
+    r_prev and receiving r), s = min(1, norm_threshold / |d|) (norm_threshold 0: 1) and p = s <d, t> / <t, t> over frames 1..frames and
+    columns [0, channels) of clip b, (1 + (guidance - 1)(eta - 1) p) t + (guidance - 1) s d is written to `out`
+    [clips*(frames+1)*hw, >= channels] - None: in place, over the unconditional half of `tokens` - for the step kernel to read with
+    guidance off (aa_apg_tokens: two launches).  `stats`: fp32 [clips, 2], receives (s_b, p_b).  The fp64 workspace is kept per
+    (device, geometry).  Returns `out`."""
+    lib = _lib.get()
+    clips, channels, frames, hw = int(clips), int(channels), int(frames), int(hw)
+    rows = clips * (frames + 1) * hw
+    if out is None:
+        out = tokens[:max(rows, 0)] if tokens.dim() == 2 else tokens
+    for name, t, need in (("tokens", tokens, 2 * rows), ("out", out, rows)):        # (a bad geometry is the entry point's to refuse)
+        _check_token_matrix("apg_tokens", name, t, tokens, "both", ("tokens", tokens), need if min(clips, channels, frames, hw) >= 1 else None, channels)
+    for name, t, count in (("momentum_buf", momentum_buf, clips * frames * hw * channels), ("stats", stats, 2 * clips)):
+        if t is None:
+            continue
+        _check(t)
+        if t.dtype != torch.float32 or t.numel() != max(count, 0) or t.device != tokens.device or not t.is_contiguous():
+            raise RuntimeError(f"apg_tokens: {name} must be fp32, contiguous, {max(count, 0)} elements, on the tokens' device")
+    d = AaApg()
+    d.tokens, d.out, d.momentum_buf, d.stats = _ptr(tokens), _ptr(out), _ptr(momentum_buf), _ptr(stats)
+    d.clips, d.channels, d.frames, d.hw = clips, channels, frames, hw
+    d.ld, d.out_ld = tokens.stride(0), out.stride(0)
+    d.guidance, d.eta, d.norm_threshold, d.momentum, d.dtype = float(guidance), float(eta), float(norm_threshold), float(momentum), _DT[tokens.dtype]
+    nbytes = lib.aa_apg_workspace(C.byref(d))
+    key = (str(tokens.device), clips, channels, frames, hw)
+    ws = _APG_WS.get(key)
+    if ws is None or ws.numel() * 8 < nbytes:
+        ws = _APG_WS[key] = torch.empty(max(nbytes // 8, 1), dtype=torch.float64, device=tokens.device)
+    _run(lib.aa_apg_tokens, C.byref(d), _ptr(ws), ws.numel() * 8, _stream(tokens))
     return out
 
 

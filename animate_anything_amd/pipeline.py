@@ -110,6 +110,75 @@ def _check_guidance_rescale(guidance_rescale):
     return r
 
 
+APG_DEFAULTS = dict(eta=0.0, norm_threshold=0.0, momentum=0.0)
+
+
+def check_apg(apg):
+    """The `apg` argument (Adaptive Projected Guidance: Sadat, Hilliges, Weber, "Eliminating Oversaturation and Artifacts of High
+    Guidance Scales in Diffusion Models", 2024): None (off), or a mapping with the keys of APG_DEFAULTS - `eta` (the weight left to the
+    part of the guidance update parallel to the text prediction; 1 is plain guidance, default 0), `norm_threshold` (the update's norm
+    is clipped to it; 0, the default: no clipping) and `momentum` (of the running update, |momentum| < 1; 0, the default: none) - any
+    of them left out taking its default.  An unknown key, a value that is no finite number, a negative threshold or |momentum| >= 1
+    raises ValueError.  Returns the completed dict, or None.
+    The paper's recommended ranges: eta in [0, 1) (0 in most of its experiments), a negative momentum between -0.75 and -0.25 (-0.5
+    for most models) and a norm_threshold between 2.5 and 15 at ITS models' latent sizes; the threshold is a norm over the whole clip
+    (channels * frames * h * w elements here), so it does not carry over from an image model.  Nobody has tuned any of the three for
+    this model."""
+    if apg is None:
+        return None
+    if not hasattr(apg, "keys"):
+        raise ValueError(f"apg {apg!r}: None, or a mapping with keys from {sorted(APG_DEFAULTS)}")
+    unknown = sorted(set(apg.keys()) - set(APG_DEFAULTS))
+    if unknown:
+        raise ValueError(f"apg: unknown key(s) {unknown} (known: {sorted(APG_DEFAULTS)})")
+    a = dict(APG_DEFAULTS)
+    for key in apg.keys():
+        v = apg[key]
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not np.isfinite(v):
+            raise ValueError(f"apg.{key} = {v!r}: a finite number")
+        a[key] = float(v)
+    if a["norm_threshold"] < 0.0:
+        raise ValueError(f"apg.norm_threshold = {a['norm_threshold']}: not negative (0: no clipping)")
+    if abs(a["momentum"]) >= 1.0:
+        raise ValueError(f"apg.momentum = {a['momentum']}: |momentum| < 1")
+    return a
+
+
+def adaptive_projected_guidance(pred_uncond, pred_text, guidance_scale, eta=0.0, norm_threshold=0.0, momentum=0.0, running=None):
+    """Adaptive Projected Guidance as a torch expression (the definition of aa_apg_tokens, include/aa_mi355.h), per sample, reduced over
+    every dimension but the first: d = text - uncond; with momentum != 0, d = running = d + momentum * running (`running`: the state
+    of the previous call, None: zeros); s = min(1, norm_threshold / |d|) (norm_threshold 0: 1); p = s <d, text> / <text, text> (0 for a
+    text prediction of zeros); the result is (1 + (g - 1)(eta - 1) p) text + (g - 1) s d.  Evaluated in float64; returned as fp32 for
+    16- and 32-bit operands, float64 for float64.  Returns (guided, running) - running is None while momentum == 0."""
+    ret = torch.float64 if pred_text.dtype == torch.float64 else torch.float32
+    u, t = pred_uncond.to(torch.float64), pred_text.to(torch.float64)
+    dims = list(range(1, t.dim()))
+    d = t - u
+    if momentum != 0:
+        d = d + momentum * running.to(torch.float64) if running is not None else d
+        running = d.to(ret)
+    else:
+        running = None
+    dd, dt, tt = ((x * y).sum(dim=dims, keepdim=True) for x, y in ((d, d), (d, t), (t, t)))
+    s = torch.ones_like(dd)
+    if norm_threshold > 0:
+        clip = dd > float(norm_threshold) ** 2
+        s = torch.where(clip, float(norm_threshold) / torch.sqrt(torch.where(clip, dd, torch.ones_like(dd))), s)
+    p = torch.where(tt > 0, s * dt / torch.where(tt > 0, tt, torch.ones_like(tt)), torch.zeros_like(tt))
+    g1 = float(guidance_scale) - 1.0
+    guided = (1.0 + g1 * (float(eta) - 1.0) * p) * t + g1 * s * d
+    return guided.to(ret), running
+
+
+def _apg_setup(apg, guidance_rescale):
+    """check_apg for a sampling call: the completed dict or None; together with guidance_rescale > 0 ValueError (the two remedies are
+    not combined: each rewrites the guided prediction from the raw halves)."""
+    a = check_apg(apg)
+    if a is not None and _check_guidance_rescale(guidance_rescale) > 0.0:
+        raise ValueError("apg and guidance_rescale > 0 cannot be combined: choose one remedy for the guidance scale")
+    return a
+
+
 CONTEXT_DEFAULTS = dict(frames=16, overlap=4, weights="pyramid", closed_loop=False)
 CONTEXT_MAX_FRAMES = 64                                       # AA_WINDOW_MAX: the slots a window descriptor carries by value
 
@@ -364,7 +433,7 @@ class LatentToVideoPipeline(PretrainedPipeline):
 
     # ------------------------------------------------------------------ denoising
     def denoise(self, latents, prompt_embeds, condition_latent, mask, motion, timesteps, guidance_scale,
-                callback=None, callback_steps=1, eta=0.0, generator=None, guidance_rescale=0.0, context=None, keep=None):
+                callback=None, callback_steps=1, eta=0.0, generator=None, guidance_rescale=0.0, context=None, keep=None, apg=None):
         """The hot loop (reference pipeline.py:163-198).  `prompt_embeds` already holds [uncond; text]
         when guidance is on.  Latents are kept in fp32.
 
@@ -390,16 +459,26 @@ class LatentToVideoPipeline(PretrainedPipeline):
         reached - and (1, 0) behind the last step, so the held region ends as the known latents bit for bit; where the mask is 1 the
         launch hands the latents through untouched.  One noise tensor serves the whole call (and every FreeInit iteration).  The
         callback sees the blended latents; nothing is blended before the first step.  Under a guidance pair both ranks blend alike
-        (their generators must agree, as for eta > 0).  UniPC is refused (`_keep_setup`).  None / False: no launch, no randn."""
+        (their generators must agree, as for eta > 0).  UniPC is refused (`_keep_setup`).  None / False: no launch, no randn.
+        `apg` (check_apg; Adaptive Projected Guidance) under guidance: the step becomes session run, ops.apg_tokens - the projected
+        guided prediction written over the unconditional half of the token matrix, two launches - and the same solver kernel with
+        guidance off: the path `guidance_rescale` takes, for all three solvers.  With momentum the fp32 buffer of the running update
+        (the size of the latents) is allocated and zeroed here, so every `denoise` - every FreeInit iteration - starts afresh.  Under
+        context windows APG runs per window, in front of the merge, with one momentum buffer per window of the schedule (a
+        departure, as for guidance_rescale: the merge writes a blended frame to both halves, so the merged matrix cannot be guided
+        afterwards; norms and projections are the window's).  Under a guidance pair both ranks run it on the gathered matrix alike.
+        Together with guidance_rescale > 0: ValueError.  None, or guidance_scale <= 1: no launch, no buffer, the loop of before."""
         k = self._keep_setup(keep, condition_latent, mask, latents, generator)
         cfg = guidance_scale > 1.0
         rescale = _check_guidance_rescale(guidance_rescale) if cfg else 0.0
+        apg = _apg_setup(apg, guidance_rescale) if cfg else None
         windows = _context_schedule(context, latents.shape[2])
         sched = self.scheduler
         unet = self.unet
         if not (isinstance(sched, (DPMSolverMultistepScheduler, DDIMScheduler, UniPCMultistepScheduler)) and hasattr(unet, "session")):
             return self._denoise_generic(latents, prompt_embeds, condition_latent, mask, motion, timesteps, guidance_scale,
-                                         callback, callback_steps, eta, generator, guidance_rescale=guidance_rescale, context=context, keep=k)
+                                         callback, callback_steps, eta, generator, guidance_rescale=guidance_rescale, context=context, keep=k,
+                                         apg=apg)
         dev = latents.device
         b0, _, frames, h, w = latents.shape
         wf = frames if windows is None else len(windows[0][0])  # frames the UNet sees at a time
@@ -431,7 +510,8 @@ class LatentToVideoPipeline(PretrainedPipeline):
         ts = [int(t) for t in timesteps]
         sess.load(sample=latents if windows is None else None, cond=condition_latent, mask=mask if use_mask else None, text=text, motion=mot,
                   t=torch.full((b,), float(ts[0]) if ts else 0.0, dtype=torch.float32, device=dev))
-        guidance = guidance_scale if cfg else None
+        pre = rescale > 0.0 or apg is not None                  # the token matrix is guided in front of the solver kernel, which runs with guidance off
+        guidance = guidance_scale if cfg and not pre else None
         if windows is None:
             x = sess.inputs["sample"]                           # fp32 [b0,C,T,h,w]: updated in place by the solver kernel
         else:
@@ -439,25 +519,38 @@ class LatentToVideoPipeline(PretrainedPipeline):
             x = latents.to(torch.float32).contiguous().clone()
             descs = [ops.window_desc(win) for win in windows]
             acc = torch.empty((b0, frames, h * w, x.shape[1]), dtype=torch.float32, device=dev)
-            halves = 2 if cfg and rescale == 0.0 else 1         # a UNet output of the clip's length: [uncond clips | text clips]
+            halves = 2 if cfg and not pre else 1                # a UNet output of the clip's length: [uncond clips | text clips]
             merged = torch.zeros((halves * b0 * (frames + 1) * h * w, 8), dtype=unet.dtype, device=dev)
         step = self._solver_step(x, eta, generator)
         if k is not None:
             known, held, knoise = _keep_operands(k, x)
+        if apg is not None:                                     # the running update r, zero before the first step: one buffer per UNet run of a step
+            runs = 1 if windows is None else len(windows)
+            running = [torch.zeros(b0 * wf * h * w * x.shape[1], dtype=torch.float32, device=dev) if apg["momentum"] != 0.0 else None
+                       for _ in range(runs)]
+
+        def guide(tok, j):
+            """The guided prediction over the unconditional half of `tok`, the output of the step's j-th UNet run (in place: the next
+            session run, or gather, rewrites the matrix)."""
+            if rescale > 0.0:
+                ops.cfg_rescale_tokens(tok, b0, x.shape[1], wf, h * w, guidance_scale, rescale)
+            elif apg is not None:
+                ops.apg_tokens(tok, b0, x.shape[1], wf, h * w, guidance_scale, apg["eta"], apg["norm_threshold"], apg["momentum"],
+                               momentum_buf=running[j])
         for i, t in enumerate(ts):
             if windows is None:
                 tok = tokens()
-                if rescale > 0.0:                               # in place: the next session run (or gather) rewrites the matrix
-                    ops.cfg_rescale_tokens(tok, b0, x.shape[1], frames, h * w, guidance_scale, rescale)
+                if pre:
+                    guide(tok, 0)
             else:
-                for win in descs:                               # schedule order: a frame's first window writes `acc`, its last `merged`
+                for j, win in enumerate(descs):                 # schedule order: a frame's first window writes `acc`, its last `merged`
                     ops.window_gather_latents(x, win, out=sess.inputs["sample"])
                     wtok = tokens()
-                    if rescale > 0.0:                           # per window (a departure: the deviations are the window's, not the clip's)
-                        ops.cfg_rescale_tokens(wtok, b0, x.shape[1], wf, h * w, guidance_scale, rescale)
-                    ops.window_merge_tokens(wtok, acc, merged, win, None if rescale > 0.0 else guidance)
+                    if pre:                                     # per window (a departure: deviations, norms and projections are the window's, not the clip's)
+                        guide(wtok, j)
+                    ops.window_merge_tokens(wtok, acc, merged, win, guidance)
                 tok = merged
-            step(tok, None if rescale > 0.0 else guidance, t, i, sess.inputs["t"], float(ts[i + 1]) if i + 1 < len(ts) else float(t))
+            step(tok, guidance, t, i, sess.inputs["t"], float(ts[i + 1]) if i + 1 < len(ts) else float(t))
             if k is not None:
                 a, s = _keep_scalars(sched, ts, i)
                 ops.keep_blend(x, known, held, a, s, noise=knoise if i + 1 < len(ts) else None)
@@ -519,7 +612,7 @@ class LatentToVideoPipeline(PretrainedPipeline):
         return [torch.zeros_like(x) for _ in range(4)]
 
     def _denoise_generic(self, latents, prompt_embeds, condition_latent, mask, motion, timesteps, guidance_scale,
-                         callback=None, callback_steps=1, eta=0.0, generator=None, guidance_rescale=0.0, context=None, keep=None):
+                         callback=None, callback_steps=1, eta=0.0, generator=None, guidance_rescale=0.0, context=None, keep=None, apg=None):
         """Any scheduler with a diffusers-style `step()`: the UNet through its module `forward`, guidance and the update as
         torch expressions (the reference's own sequence, pipeline.py:165-192).  `eta` / `generator` go to a `step()` that
         names them (diffusers' prepare_extra_step_kwargs, pipeline.py:156); DDIM's variance noise is drawn here exactly as
@@ -527,11 +620,15 @@ class LatentToVideoPipeline(PretrainedPipeline):
         `rescale_noise_cfg` to the guided prediction.  `context` with a window shorter than the clip (check_context): per step the
         module forward, guidance and `rescale_noise_cfg` run per window of schedulers.context_windows, the guided predictions are
         summed in fp32 with the windows' per-frame weights, and `step()` is applied once to the whole clip.  `keep` (check_keep): the
-        blend of `denoise` behind every `step()`, as torch expressions with the same selection at the mask's endpoints."""
+        blend of `denoise` behind every `step()`, as torch expressions with the same selection at the mask's endpoints.  `apg`
+        (check_apg) under guidance: `adaptive_projected_guidance` in the place of the guidance expression, its running update kept per
+        UNet run of a step - one for the clip, or one per window of the schedule - and zero before the first step."""
         import inspect
         k = self._keep_setup(keep, condition_latent, mask, latents, generator)
         cfg = guidance_scale > 1.0
         rescale = _check_guidance_rescale(guidance_rescale) if cfg else 0.0
+        apg = _apg_setup(apg, guidance_rescale) if cfg else None
+        running = {}                                            # window number -> the running update of APG's momentum
         windows = _context_schedule(context, latents.shape[2])
         dt = self.unet.dtype
         sched = self.scheduler
@@ -547,13 +644,17 @@ class LatentToVideoPipeline(PretrainedPipeline):
             known, held, knoise = _keep_operands(k, x)
             known, held, ts = known.float(), held.float(), [int(t) for t in timesteps]
 
-        def predict(xs, t):
-            """The (guided, rescaled) fp32 prediction for the latents `xs` - the clip, or one window of it."""
+        def predict(xs, t, j=0):
+            """The (guided, rescaled) fp32 prediction for the latents `xs` - the clip, or window `j` of it."""
             x_lp = xs.to(dt)
             model_in = torch.cat([x_lp, x_lp]) if cfg else x_lp                                  # :165
             eps = self.unet(model_in, t, encoder_hidden_states=prompt_embeds, condition_latent=cond, mask=mask,
                             motion=None if motion is None else torch.as_tensor(motion, device=x.device)).sample
             e_u, e_t = (eps[: xs.shape[0]], eps[xs.shape[0]:]) if cfg else (eps, eps)
+            if apg is not None:
+                e, running[j] = adaptive_projected_guidance(e_u.float(), e_t.float(), guidance_scale, apg["eta"], apg["norm_threshold"],
+                                                            apg["momentum"], running.get(j))
+                return e
             e = e_u.float() + guidance_scale * (e_t.float() - e_u.float()) if cfg else eps.float()
             if rescale > 0.0:
                 e = rescale_noise_cfg(e, e_t.float(), rescale)
@@ -564,10 +665,10 @@ class LatentToVideoPipeline(PretrainedPipeline):
                 e = predict(x, t)
             else:
                 e = torch.zeros_like(x)
-                for idx, wn, _first, _last in windows:
+                for j, (idx, wn, _first, _last) in enumerate(windows):
                     idx = torch.as_tensor(idx, device=x.device)
                     wn = torch.tensor(wn, dtype=torch.float64).to(device=x.device, dtype=torch.float32).reshape(1, 1, -1, 1, 1)
-                    e[:, :, idx] += wn * predict(x[:, :, idx], t)
+                    e[:, :, idx] += wn * predict(x[:, :, idx], t, j)
             b, c, f, h, w = x.shape
             if isinstance(sched, DDIMScheduler) and eta > 0:
                 extra["variance_noise"] = _variance_noise(x, generator)
@@ -587,8 +688,12 @@ class LatentToVideoPipeline(PretrainedPipeline):
                  guidance_scale=9.0, negative_prompt=None, eta=0.0, generator=None, latents=None,
                  prompt_embeds=None, negative_prompt_embeds=None, output_type="np", return_dict=True,
                  callback=None, callback_steps=1, cross_attention_kwargs=None, condition_latent=None,
-                 mask=None, timesteps=None, motion=None, guidance_rescale=0.0, context=None, free_init=None, keep=None):
-        """`keep` (check_keep; None / False: off, the default): the known-region blend of inpainting samplers - what the mask holds still
+                 mask=None, timesteps=None, motion=None, guidance_rescale=0.0, context=None, free_init=None, keep=None, apg=None):
+        """`apg` (check_apg; None: off, the default): Adaptive Projected Guidance in the place of plain guidance at guidance_scale > 1
+        (`denoise`): the guidance update's part parallel to the text prediction damped by `eta`, its norm clipped to `norm_threshold`,
+        a `momentum` across the steps of one `denoise`.  DEPARTURES: applied to the model output as it comes (the paper argues on the
+        denoised prediction), per window under context windows, refused together with guidance_rescale > 0 (ValueError).
+        `keep` (check_keep; None / False: off, the default): the known-region blend of inpainting samplers - what the mask holds still
         (mask 0) is put back on the known latents, noised to the step's level, behind every solver step (`denoise`), and with
         keep.image / keep.image_mask the known pixels are pasted over the decoded fp32 video by one more ops.keep_blend in front of
         `tensor2vid`.  The noise of the call is drawn once, here, in front of the first FreeInit iteration.  Off: no launch, no randn.
@@ -602,6 +707,7 @@ class LatentToVideoPipeline(PretrainedPipeline):
         iterations (diffusers rounds them to the model dtype).  num_iters = 1, or off: one `denoise`, no extra launch, no extra randn."""
         if latents is None:
             raise ValueError("LatentToVideoPipeline expects caller-prepared `latents` (reference pipeline.py:153)")
+        apg = _apg_setup(apg, guidance_rescale)
         keep = self._keep_setup(keep, condition_latent, mask, latents, generator)
         fi = check_free_init(free_init) if free_init is not None else self.free_init
         iters = fi["num_iters"] if fi is not None else 1
@@ -626,7 +732,7 @@ class LatentToVideoPipeline(PretrainedPipeline):
             ts = self.scheduler.timesteps if timesteps is None else timesteps
             x = self.denoise(x, prompt_embeds, condition_latent, mask, motion, [int(t) for t in ts],
                              guidance_scale, callback, callback_steps, eta=eta, generator=generator, guidance_rescale=guidance_rescale,
-                             context=context, keep=keep)
+                             context=context, keep=keep, apg=apg)
         latents = x.to(self.unet.dtype)
         if self.vae is None or output_type == "latent":
             video = None

@@ -724,6 +724,49 @@ typedef struct AaCfgRescale {
 size_t aa_cfg_rescale_workspace(const AaCfgRescale* d);
 int aa_cfg_rescale_tokens(const AaCfgRescale* d, void* workspace, size_t workspace_bytes, void* stream);
 
+/* aa_apg_tokens (added under version 110: no existing descriptor or entry point changed, so AA_VERSION stays): Adaptive Projected Guidance (Sadat, Hilliges, Weber, "Eliminating Oversaturation and Artifacts of High Guidance Scales in
+ * Diffusion Models", 2024: `normalized_guidance` with `project` and the momentum buffer, in closed form) on the UNet's token-layout
+ * output, per clip b of the guided batch (u: unconditional clip b, t: text clip b):
+ *   d   = t - u                                          fp32
+ *   r   = d + momentum * r_prev ;  d = r                 only when momentum != 0; r is the state `momentum_buf` carries from call to call
+ *                                                        (the caller zeroes it before the first step)
+ *   dd  = sum d d ,  dt = sum d t ,  tt = sum t t        fp64, over the n = channels * frames * hw elements the step kernels consume:
+ *                                                        frames 1..frames of the clip, columns [0, channels)
+ *   s   = norm_threshold / sqrt(dd)   if norm_threshold > 0 and dd > norm_threshold^2, else 1    (dd = 0 gives s = 1)
+ *   p   = s dt / tt                   if tt > 0, else 0  (a text clip of zeros has no direction: the parallel part is 0)
+ *   a   = 1 + (guidance - 1)(eta - 1) p ,  c = (guidance - 1) s          formed in fp64, rounded once to fp32
+ *   out = a t + c d                                      fp32, rounded once to the storage type
+ * which is t + (g - 1)(d_orth + eta d_par) of the clipped update s d split against t.  eta = 1, norm_threshold = 0, momentum = 0 is plain
+ * guidance, u + g (t - u), up to rounding.  `tokens` is [2 * clips * (frames + 1) * hw][ld], the unconditional clips first; `out` is
+ * [clips * (frames + 1) * hw][out_ld], a separate buffer or exactly the unconditional half of `tokens` (same pointer, same pitch: in
+ * place).  Frame-0 rows and columns >= channels of `out` are never written.  The step kernel then runs on `out` with guidance off.
+ * `momentum_buf` (fp32 [clips * frames * hw][channels], dense) is read and rewritten when momentum != 0 and must be NULL otherwise;
+ * `stats` (optional, fp32 [clips][2]) receives (s_b, p_b).  n = 1 is legal.
+ * Two launches, no atomics: partial sums of d d, d t, t t (fp64) per slice of a clip into the workspace (the launch that rewrites the
+ * momentum buffer, every element by one thread), then every workgroup adds its clip's partials in a fixed order and writes its slice:
+ * a replay, a second call from the same state and the in-place form repeat the bits of an eager out-of-place call.
+ * DEPARTURE from the paper: applied to the model output as it comes, for every prediction type (where diffusers' guider applies it); the
+ * paper argues on the denoised prediction.
+ * Refused with nothing launched - AA_E_SHAPE: a null descriptor, tokens or out; clips, channels, frames or hw < 1; a pitch smaller than
+ * channels; more than 65535 clips or 2^31 token rows; guidance, eta, norm_threshold or momentum not finite; norm_threshold < 0;
+ * |momentum| >= 1; momentum != 0 with a null momentum_buf, or momentum == 0 with one; an `out` that overlaps `tokens` other than as the
+ * identical unconditional half; momentum_buf, stats or the workspace overlapping a matrix or each other.  AA_E_WORKSPACE: a null or too
+ * small workspace (aa_apg_workspace(d) bytes).  AA_E_ALIGN: tokens / out not 2-byte, momentum_buf / stats not 4-byte, workspace not
+ * 8-byte aligned.  AA_E_DTYPE: a dtype other than AA_F16 / AA_BF16. */
+typedef struct AaApg {
+    const void* tokens;       /* [2 * clips * (frames + 1) * hw][ld], unconditional clips first */
+    void* out;                /* [clips * (frames + 1) * hw][out_ld]: separate, or exactly the unconditional half of tokens */
+    float* momentum_buf;      /* fp32 [clips * frames * hw][channels] dense, read and rewritten; NULL iff momentum == 0 */
+    float* stats;             /* fp32 [clips][2] = (s_b, p_b), or NULL */
+    int32_t clips, channels, frames, hw;
+    int32_t ld, out_ld;       /* row pitches in elements (>= channels; 4 is legal) */
+    float guidance, eta, norm_threshold, momentum;
+    int32_t dtype;            /* AA_F16 / AA_BF16 */
+} AaApg;
+
+size_t aa_apg_workspace(const AaApg* d);
+int aa_apg_tokens(const AaApg* d, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Context windows (MultiDiffusion over time; the AnimateDiff ecosystem's remedy for clips longer than the UNet's trained frame window; not
  * in the reference): per step the UNet runs on overlapping windows of `window_frames` of the clip's `total_frames` latent frames, the
  * per-window predictions are blended per frame and ONE solver update is applied to the whole clip.  Both entry points carry the window by
